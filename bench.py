@@ -16,14 +16,28 @@ on one GPU and on ranks). Extra fields: steps_per_sec, roofline (the SOR
 kernel's steady launches - every cell active -, four sweeps per launch on one
 GPU, three on ranks: HIP events on the solver's stream; `achieved` = the
 24 B/cell one launch must move / launch time, `effective_sweep_*` the same per
-sweep), cpu_baseline (the oracle's lexicographic SOR loop — the reference's
-loop restated in C — on a bounded sample of the same grid, rank 0 only) and,
-at N=1, the same workload in the other order: red_black (red-black SOR with
-the proof-mode test, bit-identical to the red-black oracle; it is not the
+sweep).
+
+A plain run does only that: set up, W warmup steps, K timed steps, the line.
+--full adds the legs that take runs of their own, at N=1: cpu_baseline (the
+oracle's lexicographic SOR loop — the reference's loop restated in C — on a
+bounded sample of the same grid, and the reference binary beside it) and the
+same workload in the other order: red_black (red-black SOR with the
+proof-mode test, bit-identical to the red-black oracle; it is not the
 reference's iterate where the solve hits the cap) or, with --ordering rb,
-reference_order.
+reference_order. --no-cpu-baseline and --lex-steps 0 drop one of them.
+
+--dump-outputs DIR writes what the last timed step left, as a caller of
+step() receives it (fields u, v, p - and t for Rayleigh-Benard - plus the
+per-step SOR iteration counts and final residuals of all K steps), to
+DIR/<name>.npy in float64 (ranks above 0: DIR/<name>.rank<R>.npy, their own
+rows). A field above its share of 48 MB is stored as a fixed sample: the flat
+elements a generator seeded with 0 draws for that size, in ascending order.
+The inputs are a function of the arguments alone, so two builds run with the
+same arguments can be compared file by file.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--global-ny NY]
+                       [--full] [--dump-outputs DIR]
 For N > 1 launch with torch.distributed.run (one rank per GPU); halos and the
 residual all-reduce travel over RCCL inside libcfd_amd.so.
 
@@ -286,6 +300,33 @@ def kcase_of(case: str) -> str:
     return "cavity" if case == "rayleigh_benard" else case  # Rayleigh-Benard runs the cavity SOR kernels
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all field files of one rank together (a dump stays below 64 MB)
+
+
+def dump_outputs(solver, case: str, iters: list, resids: list, out_dir: str, rank: int) -> None:
+    """--dump-outputs: the state the last timed step left, read back through
+    the caller's own accessor (solver.field), and the K steps' return values.
+    float64 .npy files; a field above its share of DUMP_BUDGET_BYTES is stored
+    as the flat elements a default_rng(0) draws for its size, ascending."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    names = ["u", "v", "p"] + (["t"] if case == "rayleigh_benard" else [])
+    share = DUMP_BUDGET_BYTES // len(names) // 8
+    picks = {}  # size -> sample indices (u, v, p have at most three sizes)
+    for name in names:
+        a = solver.field(name).ravel()
+        if a.size > share:
+            if a.size not in picks:
+                picks[a.size] = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a[picks[a.size]]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    if rank == 0:
+        np.save(os.path.join(out_dir, "sor_iterations_per_step.npy"), np.asarray(iters, dtype=np.float64))
+        np.save(os.path.join(out_dir, "final_residual_per_step.npy"), np.asarray(resids, dtype=np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -315,19 +356,30 @@ def parse_args(argv=None):
     ap.add_argument("--lex-sweeps", type=int, default=0,
                     help="reference_order: sweeps per lexicographic-order launch (0: auto = 4; 5 for the cavity)")
     ap.add_argument("--lex-steps", type=int, default=2,
-                    help="N=1: also time this many steps in the other sweep order (0: skip); reported as "
+                    help="--full, N=1: also time this many steps in the other sweep order (0: skip); reported as "
                          "red_black (headline lex) or reference_order (headline rb)")
     ap.add_argument("--tile-rounds", type=int, default=-1,
                     help="red-black, one GPU: LDS-tile SOR launches when the grid fits this many resident rounds of "
                          "tiles (0: never; -1: the library default, 1)")
     ap.add_argument("--tune", action="append", default=[], metavar="KNOB=VALUE",
                     help="launch-planning knob (cfd_amd._lib.TUNING names; performance only, same bits)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the timed steps also time the CPU baseline (--cpu-seconds, --no-cpu-baseline) and "
+                         "the same workload in the other sweep order (--lex-steps); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's fields and the per-step SOR iterations and "
+                         "residuals to DIR/<name>.npy (float64; a large field as a fixed seeded sample)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--loopback-ranks", type=int, default=0,
                     help="test mode: run the multi-rank code path with this many ranks as host threads sharing "
                          "GPU 0 over the library's loopback transport (no RCCL; timings are not a measurement)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the timed region divided by it)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 class TorchGroup:
@@ -450,6 +502,8 @@ def run(args, rank: int, world: int, local_rank: int, comm, group, loopback: boo
     elapsed = group.max(elapsed)
     updates = group.sum(updates)
     n_gpus = world
+    if args.dump_outputs:
+        dump_outputs(solver, args.case, iters, resids, args.dump_outputs, rank)
 
     line = None
     if rank == 0:
@@ -491,6 +545,7 @@ def run(args, rank: int, world: int, local_rank: int, comm, group, loopback: boo
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
@@ -565,12 +620,13 @@ def run(args, rank: int, world: int, local_rank: int, comm, group, loopback: boo
             }
         if loopback:
             line["config"]["loopback_ranks_on_one_gpu"] = world
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg is timed at N=1 only
+        # --full: the legs that take runs of their own (a plain run stops at the headline)
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg is timed at N=1 only
             log("timing the CPU baseline ...")
             line["cpu_baseline"] = cpu_baseline(cp.nx, cp.ny, args.cpu_seconds, args.case)
             if args.case == "cavity":  # beside it: the reference's own binary on its own case (same host)
                 line["cpu_baseline"]["reference_binary"] = reference_binary()
-        if world == 1 and args.lex_steps > 0 and args.case != "rayleigh_benard":
+        if args.full and world == 1 and args.lex_steps > 0 and args.case != "rayleigh_benard":
             if args.ordering == "rb":
                 line["reference_order"] = reference_order(C, cp, args, local_rank, check_every, cells_per_launch)
             else:

@@ -13,7 +13,7 @@ if [ -z "$SKIP_TESTS" ]; then
   rc=$?; echo "smoke exit $rc"; tail -n 2 $F/smoke.log; [ $rc -ne 0 ] && exit $rc
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 300 python3 -u bench.py ${BENCH_ARGS:-} > $F/bench.json 2> $F/bench.err
+  timeout -k 10 300 python3 -u bench.py --full ${BENCH_ARGS:-} > $F/bench.json 2> $F/bench.err
   rc=$?; echo "bench exit $rc"; cat $F/bench.json; [ $rc -ne 0 ] && { tail -5 $F/bench.err; exit $rc; }
 fi
 exit 0

@@ -7,5 +7,5 @@ cat gpurun_out/final_smoke.log
 rm -rf gpurun_out/prof
 bash scripts/profile_round.sh > gpurun_out/profile_round.log 2>&1 || { tail -20 gpurun_out/profile_round.log; exit 1; }
 echo profiles ok
-timeout -k 10 300 python -u bench.py > gpurun_out/final_bench.json 2> gpurun_out/final_bench.err || { tail gpurun_out/final_bench.err; exit 1; }
-python3 -c "import json; d=json.load(open('gpurun_out/final_bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('traffic'), d.get('red_black', {}).get('value'), d['cpu_baseline'])"
+timeout -k 10 300 python -u bench.py --full > ${TMPDIR:-/tmp}/final_bench.json 2> ${TMPDIR:-/tmp}/final_bench.err || { tail ${TMPDIR:-/tmp}/final_bench.err; exit 1; }
+python3 -c "import json; d=json.load(open('${TMPDIR:-/tmp}/final_bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('traffic'), d.get('red_black', {}).get('value'), d['cpu_baseline'])"

@@ -58,12 +58,38 @@ def test_bench_rank_path_json_line(world, extra, scaling, case, order):
 
 
 def test_bench_default_is_reference_order_with_red_black_leg():
-    """N = 1, defaults: the headline in the reference's order, the red-black
-    order of the same workload beside it."""
-    d = bench("--nx", "256", "--ny", "256", "--steps", "1", "--warmup", "1", "--max-iters", "300",
+    """N = 1, defaults: the headline in the reference's order, and with --full
+    the red-black order of the same workload beside it."""
+    d = bench("--full", "--nx", "256", "--ny", "256", "--steps", "1", "--warmup", "1", "--max-iters", "300",
               "--no-cpu-baseline", "--lex-steps", "1")
     assert d["config"]["ordering"] == "lex"
     k = d["roofline"]["kernel"]  # (256^2 fits the register-resident launch)
     assert "poisson_lexw_kernel" in k or "poisson_resident_kernel<cavity,lex>" in k
     assert d["red_black"]["ordering"] == "rb" and d["red_black"]["value"] > 0
     assert "reference_order" not in d
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_repeatable_outputs(tmp_path):
+    """Without --full the line has no leg that takes a run of its own;
+    --steps sets the timed steps and ms_per_step is the timed region over
+    them; --dump-outputs writes the last step's fields and the per-step
+    returns as float64 .npy, bit-identical from run to run."""
+    import numpy as np
+
+    a = ["--nx", "200", "--ny", "136", "--steps", "3", "--warmup", "1", "--max-iters", "300"]
+    d = [bench(*a, "--dump-outputs", str(tmp_path / k)) for k in ("one", "two")]
+    for line in d:
+        assert line["full"] is False
+        assert "cpu_baseline" not in line and "red_black" not in line and "reference_order" not in line
+        assert line["steps"] == 3 and len(line["sor_iterations_per_step"]) == 3
+        assert line["ms_per_step"] == pytest.approx(line["elapsed_s"] / 3 * 1e3, rel=1e-3, abs=1e-3)
+    files = sorted(os.listdir(tmp_path / "one"))
+    assert files == ["final_residual_per_step.npy", "p.npy", "sor_iterations_per_step.npy", "u.npy", "v.npy"]
+    assert files == sorted(os.listdir(tmp_path / "two"))
+    for f in files:
+        x, y = np.load(tmp_path / "one" / f), np.load(tmp_path / "two" / f)
+        assert x.dtype == np.float64 and x.size > 0 and np.all(np.isfinite(x))
+        assert np.array_equal(x.view(np.int64), y.view(np.int64)), f
+    assert np.load(tmp_path / "one" / "sor_iterations_per_step.npy").tolist() == d[0]["sor_iterations_per_step"]
+    assert np.load(tmp_path / "one" / "p.npy").size == 202 * 138  # (whole field: below the sampling size)
+    assert np.abs(np.load(tmp_path / "one" / "u.npy")).max() > 0

@@ -338,3 +338,37 @@ def test_bench_traffic_provenance(tmp_path, monkeypatch):
         (prof / "r6_pmc_cavity_rb_64x64.json").write_text(_json.dumps(dict(rec, **stale)))
         t, src = bench.pmc_traffic("cavity", "rb", 64, 64, 66, 4, "poisson_multi_kernel<0, 4, true>")
         assert t is None and "stale" in src["reason"]
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: a field below its share of the budget is
+    written whole, a larger one as the same ascending sample of its flat
+    elements in every run; float64 files, all of them within 64 MB; ranks
+    above 0 write their own rows under their own names."""
+    import numpy as np
+
+    import bench
+
+    small = np.arange(12.0).reshape(3, 4)
+    big = np.arange(float(bench.DUMP_BUDGET_BYTES // 8)).reshape(2, -1)  # three such fields: 3x the budget
+
+    class Fields:
+        def field(self, name):
+            return {"u": big, "v": big + 0.5, "p": small}[name]
+
+    for d in ("a", "b"):
+        bench.dump_outputs(Fields(), "cavity", [7, 9], [1.5, 0.25], str(tmp_path / d), 0)
+    bench.dump_outputs(Fields(), "cavity", [7, 9], [1.5, 0.25], str(tmp_path / "a"), 2)
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["final_residual_per_step.npy", "p.npy", "p.rank2.npy", "sor_iterations_per_step.npy",
+                           "u.npy", "u.rank2.npy", "v.npy", "v.rank2.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for f, a in got.items() if "rank" not in f) <= 64 << 20
+    assert np.array_equal(got["p.npy"], small.ravel())
+    u, v = got["u.npy"], got["v.npy"]
+    assert u.size == bench.DUMP_BUDGET_BYTES // 3 // 8 and np.all(np.diff(u) > 0)  # (values are their own indices)
+    assert np.array_equal(v, u + 0.5) and np.array_equal(got["u.rank2.npy"], u)
+    assert got["sor_iterations_per_step.npy"].tolist() == [7.0, 9.0]
+    assert got["final_residual_per_step.npy"].tolist() == [1.5, 0.25]
+    for f in ("u.npy", "v.npy", "p.npy"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), got[f])
