@@ -71,6 +71,8 @@ struct PoissonCtl {
   const double* tol;   // [0] tolerance, [1] initial residual, [2] max|source| (set by tol_kernel)
   int* stop;           // [0] converged flag, [1] iteration count at convergence
   int check_every;
+  int k_base;          // iterations of this solve done before launch numbering started (a later segment of a
+                       // resident solve): check_every counts from the solve's start, iteration k_base + kk
 };
 
 __device__ __forceinline__ size_t at(const Geo& g, int j, int i) {
@@ -289,7 +291,8 @@ __device__ __forceinline__ bool pair_go_on(const PoissonCtl& ctl, int kk, int la
 
 // The reference's while condition for the iterations [ka, kb] the host gave
 // this launch (the previous launch's, or with the lagged test the one before;
-// 0 = the initial residual; others only on check_every multiples): the first
+// 0 = the initial residual; others only on check_every multiples, counted from
+// the solve's start: ctl.k_base + kk): the first
 // one that meets the tolerance ends the solve there. Returns false if this
 // launch has nothing to do (stopped now or earlier). All waves agree.
 // proof (the tested launch ran in proof mode): an iteration the proof does not
@@ -300,7 +303,7 @@ __device__ __forceinline__ bool window_go_on(const PoissonCtl& ctl, int ka, int 
   if (ctl.stop[0] != 0) return false;
   const double tol = ctl.tol[0];
   for (int kk = ka; kk <= kb; ++kk) {
-    if (!(kk == 0 || (kk >= 1 && kk % ctl.check_every == 0))) continue;
+    if (!(kk == 0 || (kk >= 1 && (ctl.k_base + kk) % ctl.check_every == 0))) continue;
     if (!pair_go_on(ctl, kk, lane, tol, proof)) {
       if (first_wave && lane == 0) {
         ctl.stop[1] = kk;

@@ -597,7 +597,7 @@ __global__ __launch_bounds__(RES_MAXW * 64, 1) void poisson_resident_kernel(Geo 
   // group gc (every one but the cap, which the loop never tests): lane-wise loads
   auto check_load = [&](int gc) -> bool {
     const int kk = gc * NS + 1 + lane;
-    const bool tested = lane < NS && kk <= K - 1 && kk % R.check_every == 0;
+    const bool tested = lane < NS && kk <= K - 1 && (R.k_base + kk) % R.check_every == 0;
     return !tested || ld_flag(R.proven + kk) != 0u;
   };
   // LEX: iterations k0 .. k0 + 7 (<= klast), lane = 8 * (k - k0) + shard:

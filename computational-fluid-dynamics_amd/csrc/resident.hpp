@@ -93,6 +93,8 @@ struct ResCtl {
   const double* tol;    // [0] tolerance, [1] initial residual, [2] max|f| (tol_kernel)
   int K;                // sweeps to run (the cap, or the replayed count)
   int check_every;      // the reference tests every iteration (1)
+  int k_base;           // red-black: iterations of the solve before this launch (a later segment): check_every
+                        // counts from the solve's start, iteration k_base + kk
   // the reference's order (LEX): exceedance bits, 8 shards of bwords words;
   // iteration k is bit k + koff (koff covers the cells that have not started)
   unsigned long long* bits;

@@ -921,7 +921,7 @@ class Solver {
   // One SOR launch over every strip: iterations k .. k+n-1, testing [ka, kb].
   template <int CASE>
   void launch_poisson(const double* const* pin, double* const* pout, int k, int n, int ka, int kb, bool replay) {
-    PoissonCtl ctl{ring, tolv, stop, P.check_every};
+    PoissonCtl ctl{ring, tolv, stop, P.check_every, it_base};
     if (tile_on) {  // one strip (plan_tiles)
       tile_launch(P.case_id, proof_launch && !replay, S[0].g, C, pin[0], pout[0], S[0].b[B_F], ctl, k, ka, kb, n,
                   tplan, march_flags | (replay ? 4 : 0) | (window_proof ? 128 : 0), st);
@@ -964,7 +964,7 @@ class Solver {
       runn = 0;
     };
     for (int kk = k; kk < k + n && kk <= P.max_iters; ++kk) {
-      if (!(kk % P.check_every == 0 || kk == P.max_iters)) continue;
+      if (!((it_base + kk) % P.check_every == 0 || kk == P.max_iters)) continue;
       const int sl = kk & (RING - 1);
       if (runn > 0 && sl == run0 + runn) {
         ++runn;
@@ -992,7 +992,7 @@ class Solver {
     const int lo_b = comm->rank > 0 ? OVL_ROWS : 0;
     const int hi_b = comm->rank < comm->nranks - 1 ? OVL_ROWS : 0;
     const int e = m & 1, pe = e ^ 1;
-    PoissonCtl ctl{ring, tolv, stop, P.check_every};
+    PoissonCtl ctl{ring, tolv, stop, P.check_every, it_base};
     if (m == 0) {  // st_b starts after st's work so far (source, tolerance, f halos)
       HIPC(hipEventRecord(ev_sync, st));
       HIPC(hipStreamWaitEvent(st_b, ev_sync, 0));
@@ -1708,12 +1708,21 @@ class Solver {
   // path (round 5: ~2.3x a later step at 1024^2). After RES_MAX_SEGMENTS
   // windows the exact path finishes the solve.
   static constexpr int RES_WINDOW_LAUNCHES = 32, RES_MAX_SEGMENTS = 8;
-  struct CapGuard {  // the segment's iteration cap in P.max_iters (every solve path reads the cap there)
-    int& ref;
-    int saved;
-    CapGuard(int& r, int v) : ref(r), saved(r) { ref = v; }
-    ~CapGuard() { ref = saved; }
+  template <class V>
+  struct ScopedSet {  // a member set for a segment and put back when the scope ends, also by an exception
+    V& ref;
+    V saved;
+    ScopedSet(V& r, V v) : ref(r), saved(r) { ref = v; }
+    ~ScopedSet() { ref = saved; }
+    ScopedSet(const ScopedSet&) = delete;
+    ScopedSet& operator=(const ScopedSet&) = delete;
   };
+  using CapGuard = ScopedSet<int>;  // the segment's iteration cap in P.max_iters (every solve path reads the cap there)
+  // Iterations of the current solve done before the segment being run: the
+  // segment's kernels and host loops number their iterations from 1, and
+  // check_every counts from the solve's start (iteration it_base + kk is
+  // tested when it is a multiple of check_every). 0 outside the segments.
+  int it_base = 0;
   double tol_host() {
     double t2[2];
     HIPC(hipMemcpyAsync(t2, tolv, sizeof t2, hipMemcpyDeviceToHost, st));
@@ -1733,6 +1742,7 @@ class Solver {
       bool done;
       {
         CapGuard cg(P.max_iters, K - kdone);
+        ScopedSet<int> ib(it_base, kdone);
         done = solve_resident(&si, k0, seg == 0);
       }
       if (done) {
@@ -1747,18 +1757,19 @@ class Solver {
       const int w = last ? K - kdone : std::min(RES_WINDOW_LAUNCHES * sweeps_per_launch(), K - kdone);
       {
         CapGuard cg(P.max_iters, w);
-        rb_fresh = false;
-        rb_exact = !last;
+        ScopedSet<int> ib(it_base, kdone);
+        ScopedSet<bool> fr(rb_fresh, false), ex(rb_exact, !last);
         solve_rb(&si, 0);
-        rb_fresh = true;
-        rb_exact = false;
       }
       kdone += si.sor_iterations;
-      // the reference stopped inside the window, the cap, or iteration kdone's
-      // exact residual (the window's last, which its launches do not test) meets
-      // the tolerance: the solve ends here
-      if (last || si.sor_iterations < w || kdone >= K || !(si.residual > tol_host())) break;
+      // the reference stopped inside the window, the cap, or iteration kdone
+      // (the window's last, which its launches do not test) is a tested one
+      // (a multiple of check_every) and its exact residual meets the
+      // tolerance: the solve ends here
+      const bool tested = kdone % std::max(1, P.check_every) == 0;
+      if (last || si.sor_iterations < w || kdone >= K || (tested && !(si.residual > tol_host()))) break;
     }
+    T.resident_segments += res_segments;
     if (out) {
       out->sor_iterations = kdone;
       out->residual = si.residual;
@@ -1788,6 +1799,7 @@ class Solver {
         break;
       }
       if (seg == 0 && T.resident_timeouts != to0) {  // (not co-resident: the exact path takes the whole solve)
+        T.resident_segments += res_segments;
         solve_lexw(out);
         return;
       }
@@ -1802,6 +1814,7 @@ class Solver {
       if (stopped || last || kdone >= K) break;
     }
     lex_hint = 0;  // (the segments keep no sampled-row hint)
+    T.resident_segments += res_segments;
     if (out) {
       out->sor_iterations = kdone;
       out->residual = res;
@@ -1890,6 +1903,7 @@ class Solver {
     R.tol = tolv;
     R.K = K;
     R.check_every = std::max(1, P.check_every);
+    R.k_base = it_base;
     HIPC(hipMemsetAsync(res_state, 0, words * sizeof(unsigned), st));
     HIPC(hipMemsetAsync(R.status, 0xff, sizeof(int), st));  // (-1 until the launch sets its status)
     HIPC(hipEventRecord(ev_a, st));
@@ -2153,7 +2167,7 @@ class Solver {
           bool pr = false;
           if (kk == 0) {
             r = t2[1];
-          } else if (kk % P.check_every == 0) {
+          } else if ((it_base + kk) % P.check_every == 0) {
             const double* slot = ring + (size_t)(kk & (RING - 1)) * RES_SHARDS * SHARD_STRIDE;
             HIPC(hipMemcpy(h_shard, slot, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost));
             r = 0.0;

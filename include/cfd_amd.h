@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define CFD_AMD_ABI_VERSION 13
+#define CFD_AMD_ABI_VERSION 14
 
 /* CFD_RAYLEIGH_BENARD (BASELINE configs[4]) has no solver in the reference
  * tree (only figures): it is the cavity's projection step with a resting lid
@@ -132,6 +132,9 @@ typedef struct cfd_timing {
                                      kinetic energy) were cut into (ABI 13) */
   long long seqsum_serial_chunks; /* of those, the chunks that ran as the plain chain of adds (the first terms
                                      from zero, binade crossings, ties); the rest were exact integer sums (ABI 13) */
+  long long resident_segments;    /* resident solves: segments (a resident launch, plus the exact window after an
+                                     iteration it left open) summed over the solves; one per solve when every
+                                     launch ran to the solve's end (ABI 14) */
 } cfd_timing;
 
 /* Which SOR kernel family ran a solve (cfd_timing.sor_kernel); every one gives the same bits for

@@ -417,6 +417,29 @@ void orc_poisson(orc_state* s, int ordering, int* iters, double* residual) {
   *residual = res;
 }
 
+/* The check_every rule of include/cfd_amd.h (red-black engines), stated once:
+ * the initial residual is tested, then only iterations that are multiples of
+ * check_every, counted from the solve's start; the cap ends the solve
+ * untested. check_every = 1 is orc_poisson's loop. */
+void orc_poisson_every(orc_state* s, int ordering, int check_every, int* iters, double* residual) {
+  if (check_every < 1) check_every = 1;
+  if (CAVLIKE(s)) {
+    const size_t n = (size_t)(s->P.ny + 2) * (size_t)(s->P.nx + 2);
+    memset(s->f[ORC_F_P], 0, n * sizeof(double));
+  }
+  double res;
+  const double tol = solve_tolerance(s, &res);
+  int it = 0;
+  if (res > tol)
+    while (it < s->P.max_iters) {
+      ++it;
+      res = sor_iteration(s, ordering);
+      if (it % check_every == 0 && !(res > tol)) break;
+    }
+  *iters = it;
+  *residual = res;
+}
+
 void orc_poisson_fixed(orc_state* s, int ordering, int n_iters, double* residual) {
   double res = 0.0;
   for (int k = 0; k < n_iters; ++k) res = sor_iteration(s, ordering);

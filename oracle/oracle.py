@@ -61,6 +61,7 @@ def lib() -> ctypes.CDLL:
         L.orc_source.argtypes = [ctypes.c_void_p]
         ip, dp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
         L.orc_poisson.argtypes = [ctypes.c_void_p, ctypes.c_int, ip, dp]
+        L.orc_poisson_every.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ip, dp]
         L.orc_poisson_fixed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, dp]
         L.orc_step.argtypes = [ctypes.c_void_p, ctypes.c_int, ip, dp]
         L.orc_stats.argtypes = [ctypes.c_void_p, dp, dp]
@@ -121,9 +122,20 @@ class Oracle:
     def source(self) -> float:
         return lib().orc_source(self.h)
 
-    def poisson(self, ordering: int | None = None) -> tuple[int, float]:
+    def poisson(self, ordering: int | None = None, check_every: int = 1) -> tuple[int, float]:
+        """check_every > 1: the stop rule on multiples of check_every only (orc_poisson_every)."""
         it, res = ctypes.c_int(), ctypes.c_double()
-        lib().orc_poisson(self.h, self.ordering if ordering is None else ordering, ctypes.byref(it), ctypes.byref(res))
+        o = self.ordering if ordering is None else ordering
+        if check_every == 1:
+            lib().orc_poisson(self.h, o, ctypes.byref(it), ctypes.byref(res))
+        else:
+            lib().orc_poisson_every(self.h, o, check_every, ctypes.byref(it), ctypes.byref(res))
+        return it.value, res.value
+
+    def poisson_every(self, check_every: int, ordering: int | None = None) -> tuple[int, float]:
+        it, res = ctypes.c_int(), ctypes.c_double()
+        lib().orc_poisson_every(self.h, self.ordering if ordering is None else ordering, check_every,
+                                ctypes.byref(it), ctypes.byref(res))
         return it.value, res.value
 
     def poisson_fixed(self, n: int, ordering: int | None = None) -> float:
@@ -152,7 +164,32 @@ class Oracle:
     def nusselt(self) -> float:
         return lib().orc_nusselt(self.h)
 
-    def step(self) -> tuple[int, float]:
+    def step(self, check_every: int = 1) -> tuple[int, float]:
+        if check_every > 1:
+            return self.step_phases(check_every)
         it, res = ctypes.c_int(), ctypes.c_double()
         lib().orc_step(self.h, self.ordering, ctypes.byref(it), ctypes.byref(res))
         return it.value, res.value
+
+    def step_phases(self, check_every: int) -> tuple[int, float]:
+        """orc_step composed from the phases, in its order for the case, with
+        the solve's stop rule tested every check_every iterations."""
+        case = self.cp.case_id
+        if case in (0, 3):  # cavity, Rayleigh-Benard
+            self.velocity_bc(False)
+            if case == 3:
+                self.temperature_bc()
+            self.tentative()
+            if case == 3:
+                self.thermal()
+            self.source()
+            r = self.poisson_every(check_every)
+            self.correct()
+            return r
+        self.tentative()
+        self.velocity_bc(True)
+        self.source()
+        r = self.poisson_every(check_every)
+        self.correct()
+        self.velocity_bc(False)
+        return r

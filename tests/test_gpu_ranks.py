@@ -14,6 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import cfd_amd as C  # noqa: E402
+import oracle as O  # noqa: E402
 from cfd_amd import _lib  # noqa: E402
 from cfd_amd.dist import strip_rows  # noqa: E402
 
@@ -94,14 +95,24 @@ def test_rank_path_equals_single_domain(case, world, steps):
 def test_rank_path_check_every_8():
     """check_every=8 (an option; every GPU count defaults to 1, the reference's
     rule): the solve may run up to 7 sweeps past the reference's stopping
-    point, never fewer, and still converges."""
+    point, never fewer, and still converges - at the oracle's iteration
+    (the stop rule on multiples of 8 counted from the solve's start), with its
+    residual and, on the owned rows, its pressure, bit for bit."""
     cp = C.reference_defaults("cavity")
     res = run_ranks(cp, 2, 5, check_every=8)
     _, its = single(cp, 5)
+    o = O.Oracle(cp, ordering=O.RB)
+    its_o = [o.step(check_every=8) for _ in range(5)]
+    assert any(k8 != k1 for (k8, _), (k1, _r) in zip(its_o, its))  # (check_every decides a stop here)
     for r in res:
         for (ig, rg), (i1, _r1) in zip(r["its"], its):
             assert i1 <= ig <= i1 + 7
             assert ig % 8 == 0 or ig == cp.max_iters
+        assert r["its"] == its_o
+        j0, j1 = r["rows"]
+        first = 0 if j0 == 1 else j0
+        last = min(j1 + 1 if j1 == cp.ny else j1, cp.ny + 1)
+        assert np.array_equal(r["p"].view(np.int64), o.field("p")[first:last + 1].view(np.int64)), r["rows"]
 
 
 @pytest.mark.parametrize("case,world,ny,steps", [("cavity", 2, 128, 6), ("cavity", 3, 160, 4), ("channel", 2, 128, 4)])

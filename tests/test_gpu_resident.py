@@ -450,26 +450,36 @@ def test_resident_channel_rb_4096x512_equals_march():
 @pytest.mark.parametrize("order", ["rb", "lex"])
 @pytest.mark.parametrize("case", ["cavity", "channel"])
 def test_resident_check_every_equals_per_launch_paths(case, order):
-    """check_every = 3 through converging solves: red-black tests multiples
-    of 3 only (the resident launch's proofs of the tested iterations, its
+    """check_every = 3 and 5 through converging solves: red-black tests its
+    multiples only (the resident launch's proofs of the tested iterations, its
     fallback), the reference order every iteration as lexw.hpp and smlex.hip
-    do - the same counts, residuals and fields as the per-launch kernels."""
-    cp = C.make_params(case, nx=240, ny=80, max_iters=20000)
-    cp.tol_factor = 1e-3
-    out = []
-    for r in (1, 0):
-        g = C.solver_for(cp, ordering=order, small_solve="off", check_every=3, tuning={"resident": r})
-        if case == "cavity":
-            g.applyBoundaryConditions()
-        hist = [g.step() for _ in range(3)]
-        out.append((hist, g.field("p").copy(), g.timing()))
-        g.close()
-    (h1, p1, t1), (h2, p2, t2) = out
-    assert _lib.SOR_KERNEL[t1.sor_kernel] == "resident" and _lib.SOR_KERNEL[t2.sor_kernel] != "resident"
-    assert h1 == h2
-    if order == "rb":
-        assert all(k % 3 == 0 or k == cp.max_iters for k, _ in h1)
-    assert_bits(p1, p2, f"{case} {order} check_every 3 p")
+    do - the same counts, residuals and fields as the per-launch kernels.
+    Red-black: every solve stops before the cap after at least one iteration
+    (the cavity at 240x120 with tol_factor 1e-5: at 240x80 with 1e-3 the
+    tolerance, tol_factor * max|f|, is above the 1.0 the loop is primed with
+    and every solve takes 0 iterations). tests/test_gpu_check_every.py holds
+    the same solves against the oracle."""
+    if order == "rb" and case == "cavity":
+        cp = params(240, 120, max_iters=4000, tol=1e-5)
+    else:
+        cp = C.make_params(case, nx=240, ny=80, max_iters=20000)
+        cp.tol_factor = 1e-3
+    for ce in ((3, 5) if order == "rb" else (3,)):
+        out = []
+        for r in (1, 0):
+            g = C.solver_for(cp, ordering=order, small_solve="off", check_every=ce, tuning={"resident": r})
+            if case == "cavity":
+                g.applyBoundaryConditions()
+            hist = [g.step() for _ in range(3)]
+            out.append((hist, g.field("p").copy(), g.timing()))
+            g.close()
+        (h1, p1, t1), (h2, p2, t2) = out
+        assert _lib.SOR_KERNEL[t1.sor_kernel] == "resident" and _lib.SOR_KERNEL[t2.sor_kernel] != "resident"
+        assert h1 == h2, ce
+        if order == "rb":
+            assert all(0 < k < cp.max_iters for k, _ in h1), h1
+            assert all(k % ce == 0 for k, _ in h1), h1
+        assert_bits(p1, p2, f"{case} {order} check_every {ce} p")
 
 
 # ---- a solve from rest returns to the resident launch (round 6) ----

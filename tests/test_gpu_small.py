@@ -14,6 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import cfd_amd as C  # noqa: E402
+import check_every_cases as F  # noqa: E402
 import oracle as O  # noqa: E402
 from test_gpu_parity import assert_bits, ofield  # noqa: E402
 
@@ -62,12 +63,27 @@ def test_small_solve_bitexact_vs_oracle_and_multi_launch(case, kw, steps):
 
 
 def test_small_check_every_and_cap():
+    """check_every = 4 on the one-workgroup path. Converging (48x40,
+    tol_factor 1e-5, cap 4000: three steps stop at 216, 220, 220 where
+    check_every = 1 stops at 214, 219, 221): every stop a multiple of 4, the
+    oracle's counts, residuals and fields, and the multi-launch path's. Capped
+    (cap 57, no multiple of 4): every solve runs to the cap."""
+    cp = F.params("E")
+    its_s, f_s, tm = run_gpu(cp, F.steps("E"), small=True, check_every=4)
+    its_m, f_m, _ = run_gpu(cp, F.steps("E"), small=False, check_every=4)
+    ref = F.oracle_result("E", 4)
+    assert tm.poisson_launches == len(its_s)
+    assert all(0 < i < cp.max_iters and i % 4 == 0 for i, _ in its_s), its_s
+    assert its_s == ref["its"] and its_s == its_m
+    for n in ("u", "v", "p"):
+        assert_bits(f_s[n], ref[n], f"check_every 4 vs oracle {n}")
+        assert_bits(f_s[n], f_m[n], f"check_every 4 vs multi-launch {n}")
     cp = C.make_params("cavity", nx=48, ny=40, max_iters=57)
     its_s, f_s, _ = run_gpu(cp, 6, small=True, check_every=4)
     its_m, f_m, _ = run_gpu(cp, 6, small=False, check_every=4)
     assert its_s == its_m
-    assert any(i == 57 for i, _ in its_s) or all(i % 4 == 0 for i, _ in its_s)
-    assert_bits(f_s["p"], f_m["p"], "check_every 4")
+    assert all(i == 57 for i, _ in its_s)
+    assert_bits(f_s["p"], f_m["p"], "check_every 4, capped")
 
 
 def test_over_the_limit_takes_multi_launch():
