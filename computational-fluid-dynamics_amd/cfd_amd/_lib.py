@@ -49,7 +49,22 @@ SWITCH = {"auto": 0, "on": 1, "off": 2}  # enum cfd_switch
 TUNING = {"pair_wps": 0, "wave_wps": 1, "lexw_waves": 2, "lexw_edge_pct": 3, "pair_edge_pct": 4,
           "march_min_th": 5, "tent_th": 6, "lexw_ramp_pct": 7, "tile_rounds": 8, "march_order": 9,
           "lexw_left": 10, "resident": 11, "lexw_updown": 12}  # enum cfd_tuning
-SOR_KERNEL = {0: "none", 1: "march", 2: "tile", 3: "small", 4: "lexw", 5: "lex", 6: "smlex", 7: "resident"}  # enum cfd_sor_kernel
+SOR_KERNEL = {0: "none", 1: "march", 2: "tile", 3: "small", 4: "lexw", 5: "lex", 6: "smlex", 7: "resident",
+              8: "multigrid"}  # enum cfd_sor_kernel
+
+
+POISSON = {"sor": 0, "multigrid": 1}  # enum cfd_poisson_method
+
+
+class MgOptions(ctypes.Structure):
+    """cfd_mg_options: 0 keeps the default (2, 2, 50)."""
+    _fields_ = [("pre_sweeps", ctypes.c_int), ("post_sweeps", ctypes.c_int), ("max_cycles", ctypes.c_int)]
+
+
+class MgInfo(ctypes.Structure):
+    _fields_ = [("levels", ctypes.c_int), ("coarse_nx", ctypes.c_int), ("coarse_ny", ctypes.c_int),
+                ("coarse_sweeps", ctypes.c_int), ("solves", ctypes.c_longlong), ("cycles", ctypes.c_longlong),
+                ("launches", ctypes.c_longlong), ("solve_ms", ctypes.c_double), ("fine_ms", ctypes.c_double)]
 
 
 class StepInfo(ctypes.Structure):
@@ -105,6 +120,9 @@ SIGNATURES = {
     "cfd_synchronize": (_i, [_vp]),
     "cfd_set_tuning": (_i, [_vp, _i, _i]),
     "cfd_tuning_default": (_i, [ctypes.POINTER(CfdParams), _i, _ip]),
+    "cfd_set_poisson_method": (_i, [_vp, _i, ctypes.POINTER(MgOptions)]),
+    "cfd_get_mg_info": (_i, [_vp, ctypes.POINTER(MgInfo)]),
+    "cfd_mg_plan": (_i, [ctypes.POINTER(CfdParams), _ip, _ip, _ip]),
     "cfd_comm_unique_id": (_i, [ctypes.POINTER(ctypes.c_ubyte)]),
     "cfd_comm_init": (_vp, [ctypes.POINTER(ctypes.c_ubyte), _i, _i, _i]),
     "cfd_comm_destroy": (_i, [_vp]),

@@ -41,7 +41,8 @@ class _SolverBase:
     def __init__(self, params: CaseParams | None = None, *, device: int = 0, n_strips: int = 1,
                  check_every: int = 1, chunk: int = 0, rank_rows: tuple[int, int] | None = None, comm=None,
                  ordering: str = "auto", sweeps_per_launch: int = 0, proof_test: str = "auto",
-                 small_solve: str = "auto", overlap: str = "auto", tuning: dict[str, int] | None = None):
+                 small_solve: str = "auto", overlap: str = "auto", tuning: dict[str, int] | None = None,
+                 poisson: str = "sor", mg_options: dict[str, int] | None = None):
         """ordering: "lex" (the reference's lexicographic sweep, bit-identical to the
         reference binaries on one device, on strips and on ranks), "rb" (red-black SOR)
         or "auto" (lex; Rayleigh-Benard, which has no reference solver: rb).
@@ -49,13 +50,17 @@ class _SolverBase:
         4 in proof-mode launches (the step on strips or ranks: 3), 3 (cavity) / 2 (open
         cases) in exact ones; lexicographic 4, 3 on strips); bit-identical either way.
         proof_test / small_solve / overlap: "auto" / "on" / "off" (include/cfd_amd.h).
-        tuning: launch-planning knobs (_lib.TUNING names), performance only."""
+        tuning: launch-planning knobs (_lib.TUNING names), performance only.
+        poisson: "sor" (the reference's solve, the default) or "multigrid" (V-cycles to
+        the reference's tolerance: the cavity and Rayleigh-Benard on one strip, no ranks;
+        see set_poisson_method). mg_options: pre_sweeps / post_sweeps / max_cycles."""
         self.params = params if params is not None else make_params(self.CASE)
         if self.params.case_id != self.CASE:
             raise ValueError(f"{type(self).__name__} needs case {CASE_NAMES[self.CASE]}")
         if ordering == "auto":
             ordering = "rb" if self.CASE == RAYLEIGH_BENARD else "lex"
         self.ordering = ordering
+        self.poisson = "sor"
         self._cp = to_cparams(self.params, check_every, chunk, ordering, sweeps_per_launch, proof_test,
                               small_solve, overlap)
         L = _lib.lib()
@@ -67,10 +72,40 @@ class _SolverBase:
             raise _lib.CfdError("cfd_create failed: " + L.cfd_last_error().decode(errors="replace"))
         for knob, value in (tuning or {}).items():
             self.set_tuning(knob, value)
+        if poisson != "sor" or mg_options:
+            try:
+                self.set_poisson_method(poisson, mg_options)
+            except Exception:
+                self.close()
+                raise
 
     def set_tuning(self, knob: str, value: int) -> None:
         """cfd_set_tuning: a launch-planning knob (performance only, same bits)."""
         _lib.check(_lib.lib().cfd_set_tuning(self._h, _lib.TUNING[knob], int(value)), "cfd_set_tuning")
+
+    def set_poisson_method(self, method: str, mg_options: dict[str, int] | None = None) -> None:
+        """cfd_set_poisson_method: "multigrid" makes solverPressurePoisson() / step() run
+        V(pre_sweeps, post_sweeps) cycles (defaults 2, 2; at most max_cycles, default 50)
+        until the reference's residual meets its tolerance; they then return (cycles,
+        residual). "sor" switches back. Raises CfdError naming the rule for the channel,
+        the step, strips, ranks and grids without a plan (mg_plan)."""
+        if method not in _lib.POISSON:
+            raise ValueError(f"poisson must be one of {sorted(_lib.POISSON)}, got {method!r}")
+        opt = mg_options or {}
+        unknown = set(opt) - {"pre_sweeps", "post_sweeps", "max_cycles"}
+        if unknown:
+            raise ValueError(f"unknown mg_options {sorted(unknown)}")
+        o = _lib.MgOptions(int(opt.get("pre_sweeps", 0)), int(opt.get("post_sweeps", 0)), int(opt.get("max_cycles", 0)))
+        _lib.check(_lib.lib().cfd_set_poisson_method(self._h, _lib.POISSON[method], ctypes.byref(o)),
+                   "cfd_set_poisson_method")
+        self.poisson = method
+        self._mg_max_cycles = int(opt.get("max_cycles", 0)) or 50
+
+    def mg_info(self) -> _lib.MgInfo:
+        """cfd_get_mg_info: the plan and the multigrid solves' counters and device time."""
+        info = _lib.MgInfo()
+        _lib.check(_lib.lib().cfd_get_mg_info(self._h, ctypes.byref(info)), "cfd_get_mg_info")
+        return info
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -191,8 +226,9 @@ class _SolverBase:
         for k in range(1, total + 1):
             t = k * p.dt
             it, res = self.step()
-            if it >= p.max_iters:
-                print(warning_line(p.case_id, p.max_iters, res), file=err)
+            cap = self._mg_max_cycles if self.poisson == "multigrid" else p.max_iters  # (cycles in the iteration column)
+            if it >= cap:
+                print(warning_line(p.case_id, cap, res), file=err)
             if k % p.print_interval == 0 or k == total:
                 md, ke = self.statistics()
                 nu = self.nusselt() if p.case_id == RAYLEIGH_BENARD else None
@@ -266,6 +302,16 @@ def write_vtk_arrays(params: CaseParams, filename: str, time_value: float, uc: n
     ptrs = [a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for a in arrs]
     _lib.check(_lib.lib().cfd_write_vtk_arrays(ctypes.byref(cp), filename.encode(), time_value, *ptrs),
                "write_structured_grid")
+
+
+def mg_plan(params: CaseParams) -> tuple[int, int, int]:
+    """cfd_mg_plan (host only): (levels, coarse_nx, coarse_ny) of the multigrid plan of
+    these parameters; raises CfdError naming the rule where there is none."""
+    cp = to_cparams(params)
+    lv, cx, cy = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().cfd_mg_plan(ctypes.byref(cp), ctypes.byref(lv), ctypes.byref(cx), ctypes.byref(cy)),
+               "cfd_mg_plan")
+    return lv.value, cx.value, cy.value
 
 
 def params_from_library_rb(ra: float, pr: float, nx: int = 0, ny: int = 0, dt: float = 0.0) -> _lib.CfdParams:

@@ -1,0 +1,368 @@
+// mg.hip — kernels of the multigrid pressure solve (mg.hpp).
+//
+// Levels too large for one workgroup run as plain fp64 streams over a level's
+// own rows (128-B aligned, cell (j, i) at j * pitch + i): each wave takes one
+// row x 128 columns, a lane the 16-B aligned column pair (gi, gi + 1). The
+// sweeps of one smoothing step are one launch from p to a second buffer, each
+// workgroup running them on an LDS tile with recomputed halos
+// (mg_smooth_tile_kernel); the plain form is one launch per colour, in place
+// (mg_smooth_kernel: a colour's cells read only the other colour's, so no
+// launch reads what it writes), kept for comparison. The residual is
+// formed inside the restriction (four children per coarse cell) and the
+// coarse correction's ghost layer inside the prolongation, so neither goes to
+// memory. From the first level whose cells fit one workgroup's LDS down, the
+// whole sub-cycle - smoothing, restriction, the coarsest level's SOR sweeps,
+// prolongation - is one launch of one workgroup (mg_tail_kernel): those levels
+// are launch-bound, and the arithmetic is the same per-cell functions.
+//
+// Operand order (tests/mg_reference.py, cavity-01.cpp:651-654, 670-673): the
+// indicator products are real multiplies on boundary cells (0 * x keeps x's
+// sign, as in the reference); interior cells skip them (1 * x == x), the same
+// bits. The library builds with -ffp-contract=off: no fused multiply-adds.
+#include <hip/hip_runtime.h>
+
+#include "mg.hpp"
+
+namespace cfd {
+
+namespace {
+
+__device__ __forceinline__ bool mg_interior(const MgLevel* L, int j, int i) {
+  return i > 1 && i < L->nx && j > 1 && j < L->ny;
+}
+
+struct MgCoef {
+  double ew, ee, en, cs;
+  int idx;
+};
+__device__ __forceinline__ MgCoef mg_coef(const MgLevel* L, int j, int i) {
+  MgCoef k;
+  const int w = i > 1, e = i < L->nx, n = j < L->ny, r1 = j == 1;
+  k.ew = w ? 1.0 : 0.0;
+  k.ee = e ? 1.0 : 0.0;
+  k.en = n ? 1.0 : 0.0;
+  k.cs = r1 ? L->cS : 1.0;
+  k.idx = w | e << 1 | n << 2 | r1 << 3;
+  return k;
+}
+
+// Gauss-Seidel update of cell (j, i): rdiag ((ee pE + ew pW) + (en pN + cs pS) - f h2)
+__device__ __forceinline__ double mg_relax(const MgLevel* L, int j, int i, double pW, double pE, double pS, double pN,
+                                           double f) {
+  if (mg_interior(L, j, i)) return L->rdiag[7] * (((pE + pW) + (pN + pS)) - f * L->h2);
+  const MgCoef k = mg_coef(L, j, i);
+  return L->rdiag[k.idx] * (((k.ee * pE + k.ew * pW) + (k.en * pN + k.cs * pS)) - f * L->h2);
+}
+
+// SOR update of the coarsest level, the reference's form: p (1 - w) + (w rdiag) (...)
+__device__ __forceinline__ double mg_sor(const MgLevel* L, int j, int i, double pc, double pW, double pE, double pS,
+                                         double pN, double f) {
+  const MgCoef k = mg_coef(L, j, i);
+  return pc * L->one_m_omega + L->omr[k.idx] * (((k.ee * pE + k.ew * pW) + (k.en * pN + k.cs * pS)) - f * L->h2);
+}
+
+// residual ih2 (ee (pE - c) + ew (pW - c) + en (pN - c) + cs (pS - c)) - f
+__device__ __forceinline__ double mg_resid(const MgLevel* L, int j, int i, double c, double pW, double pE, double pS,
+                                           double pN, double f) {
+  if (mg_interior(L, j, i)) return L->ih2 * ((((pE - c) + (pW - c)) + (pN - c)) + (pS - c)) - f;
+  const MgCoef k = mg_coef(L, j, i);
+  return L->ih2 * (((k.ee * (pE - c) + k.ew * (pW - c)) + k.en * (pN - c)) + k.cs * (pS - c)) - f;
+}
+
+// Coarse source of cell (J, I) from a[r][c] = p(2J-2+r, 2I-2+c) (the corners
+// unused) and f of the four children (fSW = f(2J-1, 2I-1), ...).
+__device__ __forceinline__ double mg_restrict_cell(const MgLevel* Lf, int J, int I, const double (&a)[4][4], double fSW,
+                                                   double fSE, double fNW, double fNE) {
+  const int j = 2 * J - 1, i = 2 * I - 1;
+  const double rSW = mg_resid(Lf, j, i, a[1][1], a[1][0], a[1][2], a[0][1], a[2][1], fSW);
+  const double rSE = mg_resid(Lf, j, i + 1, a[1][2], a[1][1], a[1][3], a[0][2], a[2][2], fSE);
+  const double rNW = mg_resid(Lf, j + 1, i, a[2][1], a[2][0], a[2][2], a[1][1], a[3][1], fNW);
+  const double rNE = mg_resid(Lf, j + 1, i + 1, a[2][2], a[2][1], a[2][3], a[1][2], a[3][2], fNE);
+  return -0.25 * ((rSW + rSE) + (rNW + rNE));
+}
+
+// e of the coarse level with one ghost layer: north ghost = row ny, south
+// ghost = row 1 times g, then west / east ghosts = the adjacent column.
+__device__ __forceinline__ double mg_ext(const MgLevel* Lc, const double* e, int pitch, int J, int I) {
+  const int ii = min(max(I, 1), Lc->nx);
+  if (J == 0) return e[(size_t)pitch + ii] * Lc->g;
+  if (J == Lc->ny + 1) return e[(size_t)Lc->ny * pitch + ii];
+  return e[(size_t)J * pitch + ii];
+}
+
+// bilinear correction of fine cell (j, i): (((9 c + 3 V) + 3 H) + D) / 16, V / H / D the
+// coarse neighbours on the child's side (south for odd j, west for odd i)
+__device__ __forceinline__ double mg_corr(const MgLevel* Lc, const double* e, int pitch, int j, int i) {
+  const int J = (j + 1) >> 1, I = (i + 1) >> 1;
+  const int dj = (j & 1) ? -1 : 1, di = (i & 1) ? -1 : 1;
+  const double c = e[(size_t)J * pitch + I];
+  const double V = mg_ext(Lc, e, pitch, J + dj, I);
+  const double H = mg_ext(Lc, e, pitch, J, I + di);
+  const double D = mg_ext(Lc, e, pitch, J + dj, I + di);
+  return (((9.0 * c + 3.0 * V) + 3.0 * H) + D) * 0.0625;
+}
+
+// ------------------------------------------------------ multi-launch levels --
+
+// One colour of a sweep of level l. Block: 4 waves = 4 rows x 128 columns.
+__global__ __launch_bounds__(256) void mg_smooth_kernel(const MgLevel* __restrict__ lv, int l, double* p,
+                                                        const double* __restrict__ f, int colour) {
+  const MgLevel* L = lv + l;
+  const int nx = L->nx, ny = L->ny;
+  const int lane = threadIdx.x & 63;
+  const int gi = blockIdx.x * 128 + 2 * lane;  // even: a 16-B aligned pair
+  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j > ny || gi > nx) return;
+  const int t = (j + colour) & 1;  // colour 0 holds the cells with i + j even: component t of the pair
+  const int i = gi + t;
+  if (i < 1 || i > nx) return;
+  const size_t P = (size_t)L->pitch, o = (size_t)j * P + gi;
+  const double2 pc = *reinterpret_cast<const double2*>(p + o);
+  const double2 ps = *reinterpret_cast<const double2*>(p + o - P);
+  const double2 pn = *reinterpret_cast<const double2*>(p + o + P);
+  const double2 fc = *reinterpret_cast<const double2*>(f + o);
+  double v;
+  if (t == 0) v = mg_relax(L, j, i, p[o - 1], pc.y, ps.x, pn.x, fc.x);  // (i >= 2: o - 1 is column i - 1 >= 1)
+  else v = mg_relax(L, j, i, pc.x, p[o + 2], ps.y, pn.y, fc.y);        // (o + 2: column i + 1 <= nx + 1 < pitch)
+  p[o + t] = v;
+}
+
+// nsw (1..3) whole sweeps of level l in one launch, pin -> pout (as tile.hip
+// does for SOR). A workgroup of 16 waves holds a region of MG_TR rows x 128
+// columns of p in LDS: its tile plus H = 2 nsw cells of halo on every side,
+// since each colour phase leaves one more ring next to the region's border
+// stale. Phase k (colour k & 1 of sweep k >> 1) updates the cells at least
+// k + 1 from the border; after 2 nsw phases the tile itself (margin H) holds
+// what the sweeps over the whole level give - the halo cells are recomputed by
+// the neighbouring workgroups, same operands, same bits. p and f are read
+// once (1.2x with the halos) and p written once: 24-28 B per cell for nsw
+// sweeps where the colour launches move up to 48 per sweep. Lane l owns the
+// aligned column pair (2l, 2l + 1) of rows w, w + 16, ... and keeps their f
+// in registers; region column c is global column bx TW - H + c (even offset:
+// the pairs stay 16-B aligned), region row r global row by TH - H + r.
+constexpr int MG_TR = 64, MG_TC = 128, MG_TILE_THREADS = 1024, MG_TQ = MG_TR / 16;
+__global__ __launch_bounds__(MG_TILE_THREADS) void mg_smooth_tile_kernel(const MgLevel* __restrict__ lv, int l,
+                                                                         const double* __restrict__ pin,
+                                                                         double* __restrict__ pout,
+                                                                         const double* __restrict__ f, int nsw) {
+  __shared__ double S[MG_TR * MG_TC];
+  const MgLevel* L = lv + l;
+  const int nx = L->nx, ny = L->ny;
+  const int H = 2 * nsw, TW = MG_TC - 2 * H, TH = MG_TR - 2 * H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c0 = 2 * lane;
+  const int gx = (int)blockIdx.x * TW - H + c0;  // even (or negative: outside)
+  const int gy0 = (int)blockIdx.y * TH - H;
+  const size_t P = (size_t)L->pitch;
+  const bool colin = gx >= 0 && gx <= nx + 1;  // (gx + 1 <= nx + 2 < pitch)
+  double2 fr[MG_TQ];
+#pragma unroll
+  for (int q = 0; q < MG_TQ; ++q) {
+    const int r = w + 16 * q, gy = gy0 + r;
+    double2 v = make_double2(0.0, 0.0);
+    fr[q] = v;
+    if (colin && gy >= 0 && gy <= ny + 1) {
+      v = *reinterpret_cast<const double2*>(pin + (size_t)gy * P + gx);
+      fr[q] = *reinterpret_cast<const double2*>(f + (size_t)gy * P + gx);
+    }
+    *reinterpret_cast<double2*>(&S[r * MG_TC + c0]) = v;
+  }
+  __syncthreads();
+  for (int k = 0; k < 2 * nsw; ++k) {
+#pragma unroll
+    for (int q = 0; q < MG_TQ; ++q) {
+      const int r = w + 16 * q, gy = gy0 + r;
+      const int t = (gy + k) & 1;  // colour k & 1: the cells with i + j + colour even (gx is even)
+      const int c = c0 + t, i = gx + t;
+      if (r > k && r < MG_TR - 1 - k && c > k && c < MG_TC - 1 - k && gy >= 1 && gy <= ny && i >= 1 && i <= nx) {
+        const int o = r * MG_TC + c;
+        S[o] = mg_relax(L, gy, i, S[o - 1], S[o + 1], S[o - MG_TC], S[o + MG_TC], t ? fr[q].y : fr[q].x);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < MG_TQ; ++q) {
+    const int r = w + 16 * q, gy = gy0 + r;
+    if (r < H || r >= H + TH || c0 < H || c0 >= H + TW || gy < 1 || gy > ny) continue;  // (H, TW even: a pair is owned whole)
+    const double2 v = *reinterpret_cast<const double2*>(&S[r * MG_TC + c0]);
+    double* o = pout + (size_t)gy * P + gx;
+    if (gx >= 1 && gx + 1 <= nx) *reinterpret_cast<double2*>(o) = v;
+    else if (gx >= 1 && gx <= nx) o[0] = v.x;
+    else if (gx + 1 >= 1 && gx + 1 <= nx) o[1] = v.y;
+  }
+}
+
+// Residual of level l + full-weighting restriction to level l + 1; e_{l+1} = 0.
+// One thread per coarse cell; block: 4 coarse rows x 64 coarse columns.
+__global__ __launch_bounds__(256) void mg_restrict_kernel(const MgLevel* __restrict__ lv, int l,
+                                                          const double* __restrict__ p, const double* __restrict__ f,
+                                                          double* __restrict__ fc, double* __restrict__ ec) {
+  const MgLevel* Lf = lv + l;
+  const MgLevel* Lc = lv + l + 1;
+  const int I = 1 + blockIdx.x * 64 + (threadIdx.x & 63);
+  const int J = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (I > Lc->nx || J > Lc->ny) return;
+  const size_t P = (size_t)Lf->pitch;
+  const size_t o = (size_t)(2 * J - 2) * P + (size_t)(2 * I - 2);  // even column: two aligned pairs per row
+  double a[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const double2 lo = *reinterpret_cast<const double2*>(p + o + r * P);
+    const double2 hi = *reinterpret_cast<const double2*>(p + o + r * P + 2);
+    a[r][0] = lo.x, a[r][1] = lo.y, a[r][2] = hi.x, a[r][3] = hi.y;
+  }
+  const double fSW = f[o + P + 1], fSE = f[o + P + 2], fNW = f[o + 2 * P + 1], fNE = f[o + 2 * P + 2];
+  const size_t oc = (size_t)J * Lc->pitch + I;
+  fc[oc] = mg_restrict_cell(Lf, J, I, a, fSW, fSE, fNW, fNE);
+  ec[oc] = 0.0;
+}
+
+// p_l += interpolant of e_{l+1}. Block: 4 rows x 128 columns, a lane one aligned pair.
+__global__ __launch_bounds__(256) void mg_prolong_kernel(const MgLevel* __restrict__ lv, int l, double* __restrict__ p,
+                                                         const double* __restrict__ ec) {
+  const MgLevel* L = lv + l;
+  const MgLevel* Lc = lv + l + 1;
+  const int nx = L->nx, ny = L->ny;
+  const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
+  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j > ny || gi > nx) return;
+  const size_t o = (size_t)j * L->pitch + gi;
+  const int pc = Lc->pitch;
+  if (gi >= 1 && gi + 1 <= nx) {
+    double2 v = *reinterpret_cast<const double2*>(p + o);
+    v.x += mg_corr(Lc, ec, pc, j, gi);
+    v.y += mg_corr(Lc, ec, pc, j, gi + 1);
+    *reinterpret_cast<double2*>(p + o) = v;
+  } else if (gi >= 1) {
+    p[o] += mg_corr(Lc, ec, pc, j, gi);  // (gi == nx)
+  } else {
+    p[o + 1] += mg_corr(Lc, ec, pc, j, 1);  // (gi == 0; nx >= 2)
+  }
+}
+
+// ------------------------------------------------------- one-launch tail --
+
+// one colour of a sweep of a level held in LDS (rows of nx + 2), by the whole workgroup
+__device__ __forceinline__ void tail_half_sweep(const MgLevel* L, double* p, const double* f, int colour, bool sor) {
+  const int nx = L->nx, ny = L->ny, pitch = nx + 2, hw = (nx + 1) >> 1;
+  for (int q = threadIdx.x; q < ny * hw; q += MG_TAIL_THREADS) {
+    const int j = 1 + q / hw;
+    const int i = 1 + ((j + 1 + colour) & 1) + 2 * (q % hw);
+    if (i > nx) continue;
+    const int o = j * pitch + i;
+    p[o] = sor ? mg_sor(L, j, i, p[o], p[o - 1], p[o + 1], p[o - pitch], p[o + pitch], f[o])
+               : mg_relax(L, j, i, p[o - 1], p[o + 1], p[o - pitch], p[o + pitch], f[o]);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(MG_TAIL_THREADS) void mg_tail_kernel(const MgLevel* __restrict__ lv, int l0, int last,
+                                                                  int nu1, int nu2, const double* __restrict__ fg,
+                                                                  double* __restrict__ eg) {
+  __shared__ double S[MG_LDS_DOUBLES];
+  const int tid = threadIdx.x;
+  // every level's correction starts from zero, ghosts included
+  for (int l = l0; l <= last; ++l) {
+    const MgLevel* L = lv + l;
+    const int n = (L->nx + 2) * (L->ny + 2);
+    for (int q = tid; q < n; q += MG_TAIL_THREADS) S[L->lds_p + q] = 0.0;
+  }
+  {
+    const MgLevel* L = lv + l0;
+    const int nx = L->nx;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      S[L->lds_f + j * (nx + 2) + i] = fg[(size_t)j * L->pitch + i];
+    }
+  }
+  __syncthreads();
+  for (int l = l0; l < last; ++l) {
+    const MgLevel* L = lv + l;
+    const MgLevel* Lc = L + 1;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    for (int s = 0; s < nu1; ++s) {
+      tail_half_sweep(L, p, f, 0, false);
+      tail_half_sweep(L, p, f, 1, false);
+    }
+    const int pf = L->nx + 2, ncx = Lc->nx, pcp = ncx + 2;
+    for (int q = tid; q < ncx * Lc->ny; q += MG_TAIL_THREADS) {
+      const int J = 1 + q / ncx, I = 1 + q % ncx;
+      const int o = (2 * J - 2) * pf + 2 * I - 2;
+      double a[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[r][c] = p[o + r * pf + c];
+      S[Lc->lds_f + J * pcp + I] =
+          mg_restrict_cell(L, J, I, a, f[o + pf + 1], f[o + pf + 2], f[o + 2 * pf + 1], f[o + 2 * pf + 2]);
+    }
+    __syncthreads();
+  }
+  {
+    const MgLevel* L = lv + last;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    for (int s = 0; s < L->coarse_sweeps; ++s) {
+      tail_half_sweep(L, p, f, 0, true);
+      tail_half_sweep(L, p, f, 1, true);
+    }
+  }
+  for (int l = last - 1; l >= l0; --l) {
+    const MgLevel* L = lv + l;
+    const MgLevel* Lc = L + 1;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    const double* e = S + Lc->lds_p;
+    const int nx = L->nx, pf = nx + 2;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      p[j * pf + i] += mg_corr(Lc, e, Lc->nx + 2, j, i);
+    }
+    __syncthreads();
+    for (int s = 0; s < nu2; ++s) {
+      tail_half_sweep(L, p, f, 0, false);
+      tail_half_sweep(L, p, f, 1, false);
+    }
+  }
+  {
+    const MgLevel* L = lv + l0;
+    const int nx = L->nx;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      eg[(size_t)j * L->pitch + i] = S[L->lds_p + j * (nx + 2) + i];
+    }
+  }
+}
+
+}  // namespace
+
+void mg_smooth_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* f, int colour, void* stream) {
+  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
+  mg_smooth_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, colour);
+}
+
+void mg_smooth_tile_launch(const MgLevel* dlv, const MgLevel& L, int l, const double* pin, double* pout, const double* f,
+                           int nsw, void* stream) {
+  const int H = 2 * nsw;
+  const dim3 grid(L.nx / (MG_TC - 2 * H) + 1, L.ny / (MG_TR - 2 * H) + 1);
+  mg_smooth_tile_kernel<<<grid, MG_TILE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, pin, pout, f, nsw);
+}
+
+void mg_restrict_launch(const MgLevel* dlv, const MgLevel& Lc, int l, const double* p, const double* f, double* fc,
+                        double* ec, void* stream) {
+  const dim3 grid((Lc.nx + 63) / 64, (Lc.ny + 3) / 4);
+  mg_restrict_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, fc, ec);
+}
+
+void mg_prolong_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* ec, void* stream) {
+  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
+  mg_prolong_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, ec);
+}
+
+void mg_tail_launch(const MgLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream) {
+  mg_tail_kernel<<<1, MG_TAIL_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l0, last, nu1, nu2, fg, eg);
+}
+
+}  // namespace cfd

@@ -1,0 +1,70 @@
+// mg.hpp — geometric multigrid for the cavity-like pressure equation (the
+// cavity and Rayleigh-Benard): the plan (host only, params.cpp)
+// and the launches of mg.hip. No HIP types here, so host-only code may
+// include it (streams travel as void*, like comm.hip's).
+//
+// The operator is the reference's (cavity-01.cpp:643-677): Neumann west, east
+// and north, and a Dirichlet zero in the bottom ghost row (eps_s = j_min = 1
+// and the ghost row of the fresh pressure field stays 0), i.e. p = 0 at
+// y = -h/2. Level l (spacing 2^l h) keeps that zero where the finest grid has
+// it: its row 1 sees it d_l = 0.5 + 0.5^(l+1) spacings away, so the south
+// coefficient of row 1 is cS_l = 1/d_l. A coarse level that moved the zero to
+// its own ghost centre (-H/2) makes the cycle diverge.
+//
+// A V(nu1, nu2) cycle: red-black Gauss-Seidel sweeps, residual + full-weighting
+// restriction (the residual never reaches memory), the coarsest level by a
+// fixed number of SOR sweeps in one workgroup, bilinear prolongation added to
+// p. Every constant is formed on the host; the kernels add, subtract and
+// multiply in the order tests/mg_reference.py states, so cycle counts,
+// residuals and p are that restatement's, bit for bit.
+#pragma once
+
+#include <string>
+
+#include "../../include/cfd_amd.h"
+
+namespace cfd {
+
+constexpr int MG_MAX_LEVELS = 16;
+constexpr int MG_COARSE_CELLS = 4096;   // the coarsest level holds at most this many cells
+constexpr int MG_LDS_DOUBLES = 18432;   // 144 KiB: p and f of every level of the one-launch tail
+constexpr int MG_TAIL_THREADS = 1024;
+
+struct MgLevel {
+  int nx, ny;        // interior cells
+  int pitch;         // global memory: cell (j, i) at j * pitch + i, rows 0 .. ny+1 (128-B aligned rows)
+  int lds_p, lds_f;  // one-launch tail: offsets (doubles) of p and f in LDS, rows of nx + 2 (-1: not in the tail)
+  int coarse_sweeps; // 4 max(nx, ny): SOR sweeps when this level is the coarsest
+  double h2, ih2;    // 4^l (dx dx) and its reciprocal
+  double cS, g;      // south coefficient of row 1 (1 / d_l); ghost factor 1 - 1 / d_l of the prolongation
+  double rdiag[16];  // 1 / (ew + ee + en + cs), index ew | ee << 1 | en << 2 | (row 1) << 3
+  double one_m_omega;  // coarsest SOR: 1 - omega_c, omega_c = 2 / (1 + sin(pi / (max(nx, ny) + 1)))
+  double omr[16];      // omega_c * rdiag
+};
+
+struct MgPlan {
+  int levels = 0;
+  int tail = 0;  // levels tail .. levels-1 run as one launch (tail >= 1)
+  MgLevel lv[MG_MAX_LEVELS];
+};
+
+// The plan of a parameter block, or false with the rule that refused it in
+// `why` (host only: params.cpp).
+bool mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why);
+
+// Launches (mg.hip). dlv: the plan's levels in device memory; L: the host copy.
+// One colour of a red-black Gauss-Seidel sweep of level l, in place.
+void mg_smooth_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* f, int colour, void* stream);
+// nsw (1..3) whole sweeps of level l in one launch on LDS tiles, pin -> pout (both with zero ghost cells).
+void mg_smooth_tile_launch(const MgLevel* dlv, const MgLevel& L, int l, const double* pin, double* pout, const double* f,
+                           int nsw, void* stream);
+// f_{l+1} = -1/4 sum of the residual over each coarse cell's four children; e_{l+1} = 0.
+void mg_restrict_launch(const MgLevel* dlv, const MgLevel& Lc, int l, const double* p, const double* f, double* fc,
+                        double* ec, void* stream);
+// p_l += bilinear interpolant of e_{l+1} (its ghost layer formed on the fly).
+void mg_prolong_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* ec, void* stream);
+// The sub-cycle over levels l0 .. last in one workgroup, p and f of every level in LDS:
+// f_{l0} read from fg, the correction e_{l0} written to eg.
+void mg_tail_launch(const MgLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
+
+}  // namespace cfd

@@ -9,8 +9,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 
 #include "internal.hpp"
+#include "mg.hpp"
 
 namespace {
 
@@ -189,4 +191,97 @@ extern "C" int cfd_tuning_default(const cfd_params* p, int knob, int* value) {
       cfd::set_last_error("unknown tuning knob");
       return CFD_E_ARG;
   }
+}
+
+// ------------------------------------------------------------ multigrid --
+// The plan of the multigrid pressure solve (mg.hpp): level 0 is
+// the solver's grid; level l+1 (half the cells per direction) exists while
+// both sizes of level l are even and the smaller is at least 8. Valid with at
+// least two levels and a coarsest level of at most MG_COARSE_CELLS cells.
+// Every constant the kernels multiply with is formed here, in the operations
+// tests/mg_reference.py states.
+bool cfd::mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why) {
+  if (p.case_id != CFD_CAVITY && p.case_id != CFD_RAYLEIGH_BENARD) {
+    why = "multigrid covers the cavity and Rayleigh-Benard (case rule): the channel and the step keep SOR";
+    return false;
+  }
+  if (p.nx < 2 || p.ny < 2 || !(p.dx > 0)) {
+    why = "multigrid needs a grid of at least 2 x 2 cells and dx > 0 (grid rule)";
+    return false;
+  }
+  int nx = p.nx, ny = p.ny, n = 0;
+  plan = MgPlan{};
+  for (;;) {
+    MgLevel& L = plan.lv[n];
+    L.nx = nx;
+    L.ny = ny;
+    L.pitch = ((nx + 3) + 15) / 16 * 16;  // the solver's own row pitch rule (level 0: its p and f buffers)
+    L.lds_p = L.lds_f = -1;
+    const int m = std::max(nx, ny);
+    L.coarse_sweeps = 4 * m;
+    L.h2 = std::ldexp(1.0, 2 * n) * (p.dx * p.dx);
+    L.ih2 = 1.0 / L.h2;
+    const double d = 0.5 + std::ldexp(1.0, -(n + 1));
+    L.cS = 1.0 / d;
+    L.g = 1.0 - L.cS;
+    const double pi = 3.14159265358979323846;
+    const double omega = 2.0 / (1.0 + std::sin(pi / (m + 1)));
+    L.one_m_omega = 1.0 - omega;
+    for (int k = 0; k < 16; ++k) {
+      const double ew = k & 1, ee = (k >> 1) & 1, en = (k >> 2) & 1, cs = (k & 8) ? L.cS : 1.0;
+      L.rdiag[k] = 1.0 / (((ew + ee) + en) + cs);
+      L.omr[k] = omega * L.rdiag[k];
+    }
+    ++n;
+    if (!(nx % 2 == 0 && ny % 2 == 0 && std::min(nx, ny) >= 8) || n == MG_MAX_LEVELS) break;
+    nx /= 2;
+    ny /= 2;
+  }
+  plan.levels = n;
+  const MgLevel& C = plan.lv[n - 1];
+  if (n < 2) {
+    why = "grid " + std::to_string(p.nx) + " x " + std::to_string(p.ny) +
+          " has no multigrid plan (grid rule): a second level needs both sizes even and at least 8";
+    return false;
+  }
+  if ((long long)C.nx * C.ny > MG_COARSE_CELLS) {
+    why = "grid " + std::to_string(p.nx) + " x " + std::to_string(p.ny) + " has no multigrid plan (grid rule): its coarsest level " +
+          std::to_string(C.nx) + " x " + std::to_string(C.ny) + " holds more than " + std::to_string(MG_COARSE_CELLS) + " cells";
+    return false;
+  }
+  // the one-launch tail: from the first level (>= 1) of at most MG_COARSE_CELLS
+  // cells whose p and f, with those of every coarser level, fit the LDS
+  int tail = n - 1;
+  for (int l = n - 1; l >= 1; --l) {
+    long long need = 0;
+    for (int q = l; q < n; ++q) need += 2LL * (plan.lv[q].nx + 2) * (plan.lv[q].ny + 2);
+    if ((long long)plan.lv[l].nx * plan.lv[l].ny > MG_COARSE_CELLS || need > MG_LDS_DOUBLES) break;
+    tail = l;
+  }
+  plan.tail = tail;
+  int off = 0;
+  for (int q = tail; q < n; ++q) {
+    const int cells = (plan.lv[q].nx + 2) * (plan.lv[q].ny + 2);
+    plan.lv[q].lds_p = off;
+    plan.lv[q].lds_f = off + cells;
+    off += 2 * cells;
+  }
+  return true;
+}
+
+extern "C" int cfd_mg_plan(const cfd_params* p, int* levels, int* coarse_nx, int* coarse_ny) {
+  if (!p) {
+    cfd::set_last_error("null params");
+    return CFD_E_ARG;
+  }
+  cfd::MgPlan plan;
+  std::string why;
+  if (!cfd::mg_make_plan(*p, plan, why)) {
+    cfd::set_last_error(why);
+    return CFD_E_ARG;
+  }
+  if (levels) *levels = plan.levels;
+  if (coarse_nx) *coarse_nx = plan.lv[plan.levels - 1].nx;
+  if (coarse_ny) *coarse_ny = plan.lv[plan.levels - 1].ny;
+  return CFD_OK;
 }

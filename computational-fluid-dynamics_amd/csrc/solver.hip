@@ -24,6 +24,7 @@
 #include "open.hpp"
 #include "smlex.hpp"
 #include "seqsum.hpp"
+#include "mg.hpp"
 
 // 1: the reference order's ramp launches march the wall column tiles as two
 // half bands each (lexw.hpp LexRamp::wsplit): the wall tiles' masked march set
@@ -565,6 +566,7 @@ class Solver {
     (void)hipSetDevice(dev);
     if (st_b) (void)hipStreamSynchronize(st_b);
     if (st) (void)hipStreamSynchronize(st);
+    mg_release();
     for (auto& s : S)
       for (auto* p : s.b)
         if (p) (void)hipFree(p);
@@ -1657,7 +1659,223 @@ class Solver {
     }
   }
 
+  // ---------------------------------------------------------- multigrid --
+  // The opt-in multigrid solve (mg.hpp): cfd_set_poisson_method.
+  bool mg_on = false;
+  MgPlan mgp;
+  MgLevel* mg_dlv = nullptr;            // the plan's levels in device memory
+  std::vector<double*> mg_p, mg_f;      // levels >= 1: correction and source, rows 0 .. ny+1 of lv.pitch doubles
+  // Fused smoothing (mg_smooth_tile_kernel) writes to a second buffer: mg_q[l] for the multi-launch levels
+  // (level 0: mg_q0, laid out like the strip's p buffers, mg_q[0] its row 0); mg_cur[l] is the one that holds
+  // level l's current field. CFD_MG_FUSED=0 in the environment at cfd_set_poisson_method: one launch per colour,
+  // in place (the same bits; scripts/mg_timing.py compares the two).
+  std::vector<double*> mg_q, mg_cur;
+  double* mg_q0 = nullptr;
+  bool mg_fused = true;
+  int mg_nu1 = 2, mg_nu2 = 2, mg_max_cycles = 50;
+  cfd_mg_info mgi{};
+  hipEvent_t mg_ev[4] = {};             // around the level-0 launches of a cycle's way down / way up
+
+  void mg_release() noexcept {
+    for (double* q : mg_p)
+      if (q) (void)hipFree(q);
+    for (double* q : mg_f)
+      if (q) (void)hipFree(q);
+    for (size_t l = 1; l < mg_q.size(); ++l)
+      if (mg_q[l]) (void)hipFree(mg_q[l]);
+    if (mg_q0) (void)hipFree(mg_q0);
+    mg_q0 = nullptr;
+    mg_p.clear();
+    mg_f.clear();
+    mg_q.clear();
+    mg_cur.clear();
+    if (mg_dlv) (void)hipFree(mg_dlv);
+    mg_dlv = nullptr;
+    for (auto& e : mg_ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+    mg_on = false;
+  }
+
+  void set_poisson_method(int method, const cfd_mg_options* opt) {
+    if (method == CFD_POISSON_SOR) {
+      HIPC(hipStreamSynchronize(st));
+      mg_release();
+      mgi.levels = mgi.coarse_nx = mgi.coarse_ny = mgi.coarse_sweeps = 0;
+      return;
+    }
+    if (method != CFD_POISSON_MULTIGRID) throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
+    if (S.size() != 1) throw Error(CFD_E_ARG, "multigrid runs on one strip (strip rule): this solver has n_strips > 1");
+    if (comm) throw Error(CFD_E_ARG, "multigrid runs without ranks (rank rule): this is a rank solver");
+    const int nu1 = opt && opt->pre_sweeps ? opt->pre_sweeps : 2, nu2 = opt && opt->post_sweeps ? opt->post_sweeps : 2;
+    const int mc = opt && opt->max_cycles ? opt->max_cycles : 50;
+    if (nu1 < 0 || nu2 < 0 || nu1 + nu2 < 1 || mc < 1)
+      throw Error(CFD_E_ARG, "multigrid options: sweeps must be >= 0 with at least one per cycle, max_cycles >= 1");
+    MgPlan plan;
+    std::string why;
+    if (!mg_make_plan(P, plan, why)) throw Error(CFD_E_ARG, why);
+    if (plan.lv[0].pitch != pitch) throw Error(CFD_E_STATE, "multigrid plan pitch differs from the solver's");
+    HIPC(hipStreamSynchronize(st));
+    mg_release();
+    mgp = plan;
+    HIPC(hipMalloc(&mg_dlv, sizeof(MgLevel) * MG_MAX_LEVELS));
+    HIPC(hipMemcpy(mg_dlv, mgp.lv, sizeof(MgLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
+    mg_p.assign(mgp.levels, nullptr);
+    mg_f.assign(mgp.levels, nullptr);
+    for (int l = 1; l <= mgp.tail; ++l) {  // (levels below the tail's first live in LDS only)
+      const size_t n = (size_t)(mgp.lv[l].ny + 2) * mgp.lv[l].pitch * sizeof(double);
+      HIPC(hipMalloc(&mg_p[l], n));
+      HIPC(hipMalloc(&mg_f[l], n));
+      HIPC(hipMemsetAsync(mg_p[l], 0, n, st));  // ghost cells stay zero: no launch writes them
+      HIPC(hipMemsetAsync(mg_f[l], 0, n, st));
+    }
+    const char* fe = std::getenv("CFD_MG_FUSED");
+    mg_fused = !(fe && fe[0] == '0');
+    mg_q.assign(mgp.levels, nullptr);
+    mg_cur.assign(mgp.levels, nullptr);
+    if (mg_fused) {
+      const size_t n0 = (size_t)S[0].g.nrows * pitch * sizeof(double);
+      HIPC(hipMalloc(&mg_q0, n0));
+      HIPC(hipMemsetAsync(mg_q0, 0, n0, st));  // (its ghost cells stay zero, like p's)
+      mg_q[0] = mg_q0 + (size_t)(0 - S[0].g.row_lo) * pitch;
+      for (int l = 1; l < mgp.tail; ++l) {
+        const size_t n = (size_t)(mgp.lv[l].ny + 2) * mgp.lv[l].pitch * sizeof(double);
+        HIPC(hipMalloc(&mg_q[l], n));
+        HIPC(hipMemsetAsync(mg_q[l], 0, n, st));
+      }
+    }
+    for (auto& e : mg_ev) HIPC(hipEventCreate(&e));
+    mg_nu1 = nu1;
+    mg_nu2 = nu2;
+    mg_max_cycles = mc;
+    const MgLevel& C = mgp.lv[mgp.levels - 1];
+    mgi.levels = mgp.levels;
+    mgi.coarse_nx = C.nx;
+    mgi.coarse_ny = C.ny;
+    mgi.coarse_sweeps = C.coarse_sweeps;
+    mg_on = true;
+  }
+
+  // one V-cycle from level 0 on mg_cur[0] (p0: row 0 of the solver's p buffer) / f0; returns its launches
+  int mg_vcycle(double* p0, const double* f0) {
+    int launches = 0;
+    auto P_ = [&](int l) { return mg_cur[l]; };
+    auto F_ = [&](int l) { return l == 0 ? f0 : (const double*)mg_f[l]; };
+    auto smooth = [&](int l, int n) {
+      if (mg_fused) {  // up to 3 sweeps per launch, into the level's other buffer
+        for (int left = n; left > 0;) {
+          const int k = left == 4 ? 2 : std::min(left, 3);
+          double* a = l == 0 ? p0 : mg_p[l];
+          double* other = mg_cur[l] == a ? mg_q[l] : a;
+          mg_smooth_tile_launch(mg_dlv, mgp.lv[l], l, mg_cur[l], other, F_(l), k, st);
+          check_launch("mg_smooth_tile");
+          ++launches;
+          mg_cur[l] = other;
+          left -= k;
+        }
+        return;
+      }
+      for (int q = 0; q < n; ++q)
+        for (int colour = 0; colour < 2; ++colour) {
+          mg_smooth_launch(mg_dlv, mgp.lv[l], l, P_(l), F_(l), colour, st);
+          check_launch("mg_smooth");
+          ++launches;
+        }
+    };
+    const int tail = mgp.tail, last = mgp.levels - 1;
+    HIPC(hipEventRecord(mg_ev[0], st));
+    for (int l = 0; l < tail; ++l) {
+      smooth(l, mg_nu1);
+      mg_cur[l + 1] = mg_p[l + 1];
+      mg_restrict_launch(mg_dlv, mgp.lv[l + 1], l, P_(l), F_(l), mg_f[l + 1], mg_p[l + 1], st);
+      check_launch("mg_restrict");
+      ++launches;
+      if (l == 0) HIPC(hipEventRecord(mg_ev[1], st));
+    }
+    mg_tail_launch(mg_dlv, tail, last, mg_nu1, mg_nu2, mg_f[tail], mg_p[tail], st);
+    check_launch("mg_tail");
+    ++launches;
+    for (int l = tail - 1; l >= 0; --l) {
+      if (l == 0) HIPC(hipEventRecord(mg_ev[2], st));
+      mg_prolong_launch(mg_dlv, mgp.lv[l], l, P_(l), mg_cur[l + 1], st);
+      check_launch("mg_prolong");
+      ++launches;
+      smooth(l, mg_nu2);
+    }
+    HIPC(hipEventRecord(mg_ev[3], st));
+    return launches;
+  }
+
+  // max-norm residual (cavity-01.cpp:659-677) of the field in a buffer laid out like the strip's (final_residual's pass)
+  double mg_residual(const double* buf) {
+    Strip& s = S[0];
+    HIPC(hipMemsetAsync(resmax, 0, RES_SHARDS * SHARD_STRIDE * sizeof(double), st));
+    cavity_resmax_kernel<<<pair_grid(s), 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax);
+    check_launch("resmax");
+    HIPC(hipMemcpyAsync(h_shard, resmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    double res = 0.0;
+    for (int q = 0; q < RES_SHARDS; ++q) res = std::max(res, h_shard[q * SHARD_STRIDE]);
+    return res;
+  }
+
+  void solve_mg(cfd_step_info* out) {
+    Strip& s = S[0];
+    double* X = s.b[pbuf(pcur)];
+    // cavity-01.cpp:610-611: each solve starts from a zero field, ghosts included
+    HIPC(hipMemsetAsync(X, 0, (size_t)s.g.nrows * pitch * sizeof(double), st));
+    solve_tolerance();
+    const double tol = tol_host();
+    double* p0 = X + (size_t)(0 - s.g.row_lo) * pitch;
+    const double* f0 = s.b[B_F] + (size_t)(0 - s.g.row_lo) * pitch;
+    HIPC(hipEventRecord(ev_a, st));
+    double res = 1.0;  // cavity-01.cpp:618
+    int cycles = 0;
+    long long launches = 0;
+    double fine = 0.0;
+    mg_cur[0] = p0;
+    while (res > tol && cycles < mg_max_cycles) {
+      launches += mg_vcycle(p0, f0);
+      // the reference's max-norm residual of the cycle's field (waits for the stream)
+      res = mg_residual(mg_cur[0] == p0 ? X : mg_q0);
+      launches += 1;
+      ++cycles;
+      float a = 0.f, b = 0.f;
+      HIPC(hipEventElapsedTime(&a, mg_ev[0], mg_ev[1]));
+      HIPC(hipEventElapsedTime(&b, mg_ev[2], mg_ev[3]));
+      fine += (double)a + (double)b;
+    }
+    if (mg_cur[0] != p0) {  // (an odd number of fused launches: the field is in the second buffer)
+      HIPC(hipMemcpyAsync(p0, mg_cur[0], (size_t)(P.ny + 2) * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
+      mg_cur[0] = p0;
+    }
+    HIPC(hipEventRecord(ev_b, st));
+    HIPC(hipEventSynchronize(ev_b));
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
+    const long long sweeps = (long long)cycles * (mg_nu1 + mg_nu2);
+    T.poisson_ms += ms;
+    T.poisson_launches += launches;
+    T.poisson_sweeps += sweeps;  // (level-0 sweeps)
+    T.poisson_cell_updates += (long long)P.nx * P.ny * sweeps;
+    mgi.solves += 1;
+    mgi.cycles += cycles;
+    mgi.launches += launches;
+    mgi.solve_ms += ms;
+    mgi.fine_ms += fine;
+    if (out) {
+      out->sor_iterations = cycles;
+      out->residual = res;
+    }
+  }
+
   void solve(cfd_step_info* out) {
+    if (mg_on) {
+      T.sor_kernel = CFD_SOR_MULTIGRID;
+      solve_mg(out);
+      return;
+    }
     if (use_smlex()) {
       T.sor_kernel = CFD_SOR_SMLEX;
       solve_smlex(out);
@@ -2625,6 +2843,17 @@ int cfd_reset_timing(cfd_solver* s) {
     v->flush_step_time();
     v->flush_seq_count();
     v->T = cfd_timing{};
+    v->mgi.solves = v->mgi.cycles = v->mgi.launches = 0;
+    v->mgi.solve_ms = v->mgi.fine_ms = 0.0;
+  });
+}
+int cfd_set_poisson_method(cfd_solver* s, int method, const cfd_mg_options* opt) {
+  return guard([&] { S_(s)->set_poisson_method(method, opt); });
+}
+int cfd_get_mg_info(cfd_solver* s, cfd_mg_info* out) {
+  return guard([&] {
+    if (!out) throw Error(CFD_E_ARG, "null output");
+    *out = S_(s)->mgi;
   });
 }
 int cfd_synchronize(cfd_solver* s) { return guard([&] { HIPC(hipStreamSynchronize(S_(s)->st)); }); }

@@ -149,10 +149,49 @@ enum cfd_sor_kernel {
                          the other reference-order kernels do not take) */
   CFD_SOR_SMLEX = 6,  /* reference order, whole solve in one workgroup, p in LDS (smlex.hip): reference-sized
                          grids (ABI 9) */
-  CFD_SOR_RESIDENT = 7 /* whole solve in one persistent launch, every tile of p in registers (resident.hpp):
+  CFD_SOR_RESIDENT = 7, /* whole solve in one persistent launch, every tile of p in registers (resident.hpp):
                           the cavity and the channel, both orders, one strip of up to ~2 M cells, no ranks
                           (ABI 11) */
+  CFD_SOR_MULTIGRID = 8 /* not SOR: geometric multigrid V-cycles (mg.hip), chosen with cfd_set_poisson_method;
+                           its own field - converged where the SOR solves stop at their cap (added within ABI 14) */
 };
+
+/*
+ * Multigrid pressure solve. Added within ABI 14: new symbols and one new enum value
+ * only - no existing struct, function or default changes, and a host built against the earlier
+ * ABI 14 header runs unchanged - so CFD_AMD_ABI_VERSION stays 14.
+ *
+ * An opt-in mode for the cavity and Rayleigh-Benard on one strip without ranks. The default solve
+ * reproduces the reference's SOR, which at large grids stops at MAX_SOR_ITERS unconverged; with
+ * CFD_POISSON_MULTIGRID cfd_solve_pressure / cfd_step run V(pre, post) cycles instead (red-black
+ * Gauss-Seidel smoothing, full-weighting restriction, bilinear prolongation, the coarsest level by
+ * a fixed number of SOR sweeps) until the reference's max-norm residual meets the reference's
+ * tolerance tol_factor * max|source|, or max_cycles. cfd_step_info.sor_iterations is then the
+ * cycle count and residual that max-norm residual. max_iters, ordering, check_every and the
+ * solve-path switches play no part: the field is the same for every ordering.
+ *
+ * Plan: level 0 is the solver's grid; level l+1 (nx/2 x ny/2) exists while both sizes of level l
+ * are even and the smaller is >= 8. Valid with at least two levels and a coarsest level of at most
+ * 4096 cells (it is solved in one workgroup's LDS). cfd_mg_plan and cfd_set_poisson_method return
+ * CFD_E_ARG, cfd_last_error naming the rule, for the channel and the step (case rule), a grid
+ * without a valid plan such as the reference's 63^2 (grid rule), more than one strip (strip rule)
+ * and rank solvers (rank rule).
+ */
+enum cfd_poisson_method { CFD_POISSON_SOR = 0, CFD_POISSON_MULTIGRID = 1 };
+typedef struct cfd_mg_options {
+  int pre_sweeps, post_sweeps, max_cycles;  /* 0 (or a NULL options pointer): 2, 2, 50 */
+} cfd_mg_options;
+/* CFD_POISSON_SOR switches back: the next solves give the bits of a solver that never switched. */
+int cfd_set_poisson_method(cfd_solver* s, int method, const cfd_mg_options* opt);
+typedef struct cfd_mg_info {
+  int levels, coarse_nx, coarse_ny, coarse_sweeps;  /* the plan (0 while the mode is off) */
+  long long solves, cycles, launches;                /* since cfd_create / cfd_reset_timing */
+  double solve_ms;  /* device time of the multigrid solves, residual passes included (HIP events) */
+  double fine_ms;   /* of that, the level-0 launches (smoothing, restriction, prolongation) */
+} cfd_mg_info;
+int cfd_get_mg_info(cfd_solver* s, cfd_mg_info* out);
+/* The plan of a parameter block (host only, no device needed); any output pointer may be NULL. */
+int cfd_mg_plan(const cfd_params* p, int* levels, int* coarse_nx, int* coarse_ny);
 
 /* Library / ABI info. */
 int cfd_abi_version(void);
