@@ -157,6 +157,100 @@ def solve(f: np.ndarray, dx: float, tol_factor: float = 1e-9, nu1: int = 2, nu2:
     return cycles, res, p, hist
 
 
+MAX_LDS_DOUBLES = 18432
+
+
+def tail(pl) -> int:
+    """The first level of the one-launch tail (mg_make_plan's rule): walk from the
+    last level down to level 1, stop at a level of more than 4096 cells or where
+    p and f of it and every coarser level, ghosts included, pass 18432 doubles;
+    the tail is the lowest level reached."""
+    t = len(pl) - 1
+    for l in range(len(pl) - 1, 0, -1):
+        need = sum(2 * (a + 2) * (b + 2) for a, b in pl[l:])
+        if pl[l][0] * pl[l][1] > MAX_COARSE_CELLS or need > MAX_LDS_DOUBLES:
+            break
+        t = l
+    return t
+
+
+def smoothing_launches(nu: int, fused: bool) -> int:
+    """Launches of nu sweeps of a multi-launch level: fused, nu cut into pieces of
+    at most 3 with 4 cut as 2 + 2; otherwise one launch per colour."""
+    if not fused:
+        return 2 * nu
+    n = 0
+    while nu > 0:
+        nu -= 2 if nu == 4 else min(nu, 3)
+        n += 1
+    return n
+
+
+def launches_per_cycle(pl, nu1: int, nu2: int, fused: bool = True) -> int:
+    """Each level below the tail: its smoothing launches, the restriction and the
+    prolongation; then the tail and the residual pass."""
+    per_level = smoothing_launches(nu1, fused) + smoothing_launches(nu2, fused) + 2
+    return tail(pl) * per_level + 2
+
+
+def oracle_step(o, cp, **mg_opts):
+    """One timestep of the oracle `o` in its own phase order (Oracle.step_phases)
+    with solve() in place of its SOR loop: returns (cycles, residual)."""
+    rb = cp.case_id == 3
+    o.velocity_bc(False)
+    if rb:
+        o.temperature_bc()
+    o.tentative()
+    if rb:
+        o.thermal()
+    o.source()
+    cycles, res, p, _ = solve(o.field("src"), cp.dx, cp.tol_factor, **mg_opts)
+    o.field("p")[...] = p
+    o.correct()
+    return cycles, res
+
+
+def dense_operator(L: Level) -> np.ndarray:
+    """The level's operator as a matrix over the interior cells in row-major
+    order, column by column from residual() with a zero source."""
+    n = L.nx * L.ny
+    A = np.empty((n, n))
+    z = np.zeros((L.ny + 2, L.nx + 2))
+    for k in range(n):
+        p = np.zeros_like(z)
+        p[1 + k // L.nx, 1 + k % L.nx] = 1.0
+        A[:, k] = residual(L, p, z).ravel()
+    return A
+
+
+def direct_solve(f: np.ndarray, dx: float, refinements: int = 5):
+    """A x = f on level 0 without multigrid: a dense float64 solve refined with
+    np.longdouble residuals. Returns (x as a (ny+2, nx+2) field with zero
+    ghosts, ||A^-1||_inf, max|f - A x| of the refined x in long double)."""
+    ny, nx = f.shape[0] - 2, f.shape[1] - 2
+    A = dense_operator(Level(0, nx, ny, dx))
+    Ainv = np.linalg.inv(A)
+    b = np.ascontiguousarray(f[1:-1, 1:-1], dtype=np.float64).ravel()
+    Al, bl = A.astype(np.longdouble), b.astype(np.longdouble)
+    x = (Ainv @ b).astype(np.longdouble)
+    for _ in range(refinements):
+        r = bl - Al @ x
+        x = x + (Ainv @ r.astype(np.float64)).astype(np.longdouble)
+    rmax = float(np.abs(bl - Al @ x).max())
+    out = np.zeros_like(f, dtype=np.float64)
+    out[1:-1, 1:-1] = x.astype(np.float64).reshape(ny, nx)
+    return out, float(np.abs(Ainv).sum(axis=1).max()), rmax
+
+
+def yardstick_bound(f: np.ndarray, dx: float, p: np.ndarray, res: float, ainv_norm: float) -> float:
+    """max|p - x| <= ||A^-1||_inf (res + 48 u ih2 max|p| + u max|f|), u = 2^-53: A (p - x) = r_exact, and the
+    reference's own evaluation of r (the reported res) differs from r_exact by at most the rounding of its
+    differences, products and sums (DESIGN.md §2's bound) plus that of the final subtraction of f."""
+    u = 2.0 ** -53
+    ih2 = 1.0 / (dx * dx)
+    return ainv_norm * (res + 48.0 * u * ih2 * float(np.abs(p).max()) + u * float(np.abs(f).max()))
+
+
 def cavity_source(us: np.ndarray, vs: np.ndarray, dx: float, dt: float, rho: float) -> np.ndarray:
     """source_term as the reference builds it (cavity-01.cpp:622-627); us / vs are
     (ny+2, nx+2) with u*(j, i) the east face of cell (j, i), v*(j, i) its north face."""

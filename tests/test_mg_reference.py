@@ -14,7 +14,11 @@ import oracle as O
 TOL_FACTOR = 1e-9
 CYCLE_CAP = 15  # a cap, not a measurement: a multigrid that needs more is broken (measured: 6-7)
 
-RANDOM_GRIDS = [(64, 64), (96, 64), (240, 120), (512, 512)]
+# two-level plans (8x8 -> 4x4, 10x12 -> 5x6, 30x18 -> 15x9, 126x90 -> 63x45, 126x130 -> 63x65: 4095 cells, 260
+# coarse sweeps) and the thinnest strips the level rule allows (a coarsest level 4 cells wide)
+PLAN_GRIDS = [(8, 8), (10, 12), (30, 18), (126, 130), (126, 90), (1024, 8), (8, 1024), (512, 16), (16, 512)]
+RANDOM_GRIDS = [(64, 64), (96, 64), (240, 120), (512, 512)] + PLAN_GRIDS
+YARDSTICK_GRIDS = [(16, 16), (48, 16), (16, 48), (30, 18)]
 
 
 def random_fixture(nx, ny):
@@ -88,6 +92,15 @@ def test_unit_south_coefficient_misses_the_cap():
     (240, 120, (4, 30, 15)),
     (16, 16, (3, 4, 4)),
     (4096, 4096, (11, 4, 4)),
+    (8, 8, (2, 4, 4)),
+    (10, 12, (2, 5, 6)),
+    (30, 18, (2, 15, 9)),
+    (126, 130, (2, 63, 65)),
+    (126, 90, (2, 63, 45)),
+    (1024, 8, (2, 512, 4)),
+    (8, 1024, (2, 4, 512)),
+    (512, 16, (3, 128, 4)),
+    (16, 512, (3, 4, 128)),
 ])
 def test_mg_plan_levels(nx, ny, want):
     assert C.mg_plan(C.make_params("cavity", nx=nx, ny=ny)) == want
@@ -106,3 +119,65 @@ def test_mg_plan_refusals():
         assert "(-1)" in str(e.value)  # CFD_E_ARG
     assert M.plan(63, 63) is None and M.plan(93, 31) is None
     assert M.plan(8200, 8200) is None  # 8200 -> 4100 -> 2050 -> 1025: an odd coarsest level of over 4096 cells
+
+
+def test_tail_and_launch_counts():
+    """tail() / launches_per_cycle() against DESIGN.md §8's figures: a 4096^2 V(2,2)
+    cycle is 26 launches fused (6 multi-launch levels x 4, the tail, the residual
+    pass) and 62 with one launch per colour."""
+    pl = M.plan(4096, 4096)
+    assert M.tail(pl) == 6 and pl[6] == (64, 64)
+    assert M.launches_per_cycle(pl, 2, 2, True) == 26
+    assert M.launches_per_cycle(pl, 2, 2, False) == 62
+    assert [M.smoothing_launches(n, True) for n in range(8)] == [0, 1, 1, 1, 2, 2, 2, 3]
+    assert [M.smoothing_launches(n, False) for n in range(4)] == [0, 2, 4, 6]
+    assert M.tail(M.plan(240, 120)) == 2 and M.tail(M.plan(512, 512)) == 3  # the tail from 60x30 / 64^2
+    assert M.tail(M.plan(992, 992)) == 4  # 62^2 and 31^2 (124^2 is over 4096 cells)
+    for nx, ny in PLAN_GRIDS:  # two levels: the tail is the coarsest level alone; 512x16: 256x8 and 128x4
+        assert M.tail(M.plan(nx, ny)) == 1
+    # 126x130: the 63x65 level alone is 2 * 65 * 67 = 8710 doubles
+    assert M.launches_per_cycle(M.plan(126, 130), 2, 2, True) == 6
+    assert M.launches_per_cycle(M.plan(240, 120), 4, 1, True) == 12  # 3 smoothing launches per level
+
+
+@pytest.mark.parametrize("nx,ny", YARDSTICK_GRIDS)
+def test_restatement_solves_the_reference_equations(nx, ny):
+    """Independent of the scheme: the level-0 operator assembled from the residual that
+    test_level0_residual_is_the_reference_loop pins, solved densely and refined in long
+    double; the restatement's p is within what its reported residual allows."""
+    dx = 1.0 / nx
+    f = M.random_source(nx, ny, dx, 1e-3, seed=nx * 1000 + ny)
+    x, ainv, rmax = M.direct_solve(f, dx)
+    cycles, res, p, _ = M.solve(f, dx, TOL_FACTOR)
+    err = float(np.abs(p - x).max())
+    bound = M.yardstick_bound(f, dx, p, res, ainv)
+    print(f"{nx}x{ny}: {cycles} cycles residual {res:.3e}; refined residual {rmax:.3e}; ||A^-1|| {ainv:.3e}; "
+          f"max|p - x| {err:.3e} <= {bound:.3e}")
+    assert res <= TOL_FACTOR * np.abs(f).max() and cycles <= CYCLE_CAP
+    assert rmax <= res * 1e-3  # x is exact against what p is held to
+    assert err <= bound
+    assert not p[0].any() and not p[-1].any() and not p[:, 0].any() and not p[:, -1].any()
+
+
+def test_zero_source_is_one_cycle_of_zeros():
+    f = np.zeros((18, 18))
+    cycles, res, p, _ = M.solve(f, 1.0 / 16, TOL_FACTOR)
+    assert (cycles, res) == (1, 0.0)
+    assert not p.view(np.int64).any()
+
+
+@pytest.mark.parametrize("case,nx,ny,kw", [("cavity", 96, 64, dict(re=1000.0)),
+                                           ("cavity", 64, 64, dict(re=100.0, dt=1e-3)),
+                                           ("rayleigh_benard", 128, 32, {})])
+def test_oracle_step_converges_every_step(case, nx, ny, kw):
+    """The oracle's phases around the restatement's solve: every step within the cap,
+    p's ghost cells zero, the divergence that the corrector leaves small."""
+    cp = C.make_params(case, nx=nx, ny=ny, **kw)
+    o = O.Oracle(cp, ordering=O.RB)
+    for k in range(4):
+        cycles, res = M.oracle_step(o, cp)
+        tol = cp.tol_factor * float(np.abs(o.field("src")).max())
+        print(f"{case} {nx}x{ny} step {k + 1}: {cycles} cycles residual {res:.3e} (tol {tol:.3e})")
+        assert res <= tol and cycles <= CYCLE_CAP
+        p = o.field("p")
+        assert not p[0].any() and not p[-1].any() and not p[:, 0].any() and not p[:, -1].any()
