@@ -48,7 +48,8 @@ class _SolverBase:
         or "auto" (lex; Rayleigh-Benard, which has no reference solver: rb).
         sweeps_per_launch: SOR iterations fused per kernel launch (0 = auto: red-black
         4 in proof-mode launches (the step on strips or ranks: 3), 3 (cavity) / 2 (open
-        cases) in exact ones; lexicographic 4, 3 on strips); bit-identical either way.
+        cases) in exact ones; lexicographic 4, 3 on strips, 5 for a cavity of 4096^2
+        cells or more on one strip); bit-identical either way.
         proof_test / small_solve / overlap: "auto" / "on" / "off" (include/cfd_amd.h).
         tuning: launch-planning knobs (_lib.TUNING names), performance only.
         poisson: "sor" (the reference's solve, the default) or "multigrid" (V-cycles to

@@ -61,4 +61,7 @@ void write_pvd(const std::string& filename, const char* const* files, const doub
 
 bool host_is_fluid(const cfd_params& p, int j, int i);
 
+// sweeps per reference-order launch on one strip when sweeps_per_launch is 0 (params.cpp)
+int lexw_auto_sweeps(const cfd_params& p);
+
 }  // namespace cfd

@@ -66,9 +66,35 @@ constexpr int LEXW_SHARDS = 8;
 // 8-row halo serves up to 3 sweeps (Solver::lexw_ns keeps strips at 3).
 // At 5 sweeps (the cavity on one strip) the left halo grows to 10 columns
 // (output column 10 reads column 9 after 9 half-sweeps) and the right one to
-// 12: output columns 10..115 (106, lanes 5..57).
-__host__ __device__ constexpr int lexw_twc(int ns) { return ns >= 5 ? 106 : ns == 4 ? 110 : PAIR_TWC; }
-__host__ __device__ constexpr int lexw_ch(int ns) { return ns >= 5 ? 10 : 8; }
+// 12: output columns 10..115 (106, lanes 5..57). At 6 sweeps (h up to 12) the
+// halos are 12 and 14 columns: output columns 12..113 (102, lanes 6..56).
+__host__ __device__ constexpr int lexw_twc(int ns) {
+  return ns >= 6 ? 102 : ns == 5 ? 106 : ns == 4 ? 110 : PAIR_TWC;
+}
+__host__ __device__ constexpr int lexw_ch(int ns) { return ns >= 6 ? 12 : ns == 5 ? 10 : 8; }
+
+// The source-row ring (LexRun::fr: rows R+1 .. R+2NS of f, read-only, each
+// lane reading back only what it wrote) lives in LDS for the deep cavity
+// launches: 40 VGPRs less per lane, which is what lets 5 sweeps fit 2 waves
+// per SIMD without spills and 6 sweeps fit at all (the in-register ring also
+// ties its depth, 10, to the 10-step unroll). One 1 KiB row (64 lanes x 16 B)
+// per slot and wave, lexw_ring(NS) slots (a power of two >= 2NS), the slot of
+// a row chosen by a runtime base that advances once per loop trip. A lane
+// touches its own 16 B only and a wave's LDS operations complete in order, so
+// the ring needs no barrier (the waves of a block return at different points:
+// a block-wide barrier would hang). 4 waves x 16 slots = 64 KiB per block, two
+// blocks per CU.
+#ifndef CFD_LEXW_LDS4
+#define CFD_LEXW_LDS4 0  // 1: the cavity's 4-sweep launches take the LDS ring too (A/B build: 224.5 against
+                         // 214.3 ms per step at 4096^2 - at 203 VGPRs they gain no wave: profiles/r7/lexw_deep)
+#endif
+#ifndef CFD_LEXW_LDS_AHEAD
+#define CFD_LEXW_LDS_AHEAD 1  // 1: a sweep's source rows are read from the ring one sweep ahead (lx_sweeps)
+#endif
+__host__ __device__ constexpr bool lexw_lds(int kcase, int ns) {
+  return kcase == CAVITY && (ns >= 5 || (ns == 4 && CFD_LEXW_LDS4));
+}
+__host__ __device__ constexpr int lexw_ring(int ns) { return ns <= 4 ? 8 : 16; }
 
 // Ramp-launch tiling: bands of `th` rows from row `row0`; band b holds the
 // column tiles ca..cb (the ones its rows touch), numbered from first: band[b]
@@ -198,10 +224,12 @@ struct LxDefer {
   int k;  // iteration of the pending residual, -1: none
 };
 
-template <int NS>
+template <int NS, bool LR = false>
 struct LexRun {
   double2 w[NS][5];  // sweep S: rows R+2S .. R+2S+4
-  double2 fr[10];    // source rows R+1 .. R+10
+  double2 fr[LR ? 1 : 10];  // source rows R+1 .. R+10 (LR: in the wave's LDS ring instead, lexw_lds)
+  double2* ring;     // LR: this lane's 16 B of ring slot 0 (slot q: ring[64 q])
+  int rb;            // LR: slot base, advanced by 10 (mod lexw_ring) once per loop trip
   double2 np[5];     // prefetched p_in rows R .. R-4
   double2 nf[5];     // prefetched f rows R+1 .. R-3
   unsigned long long mask;  // bit t/2: a residual of this lane's iteration Bd0 + t/2 - lane exceeds tol
@@ -651,8 +679,20 @@ __device__ __forceinline__ void lxo_row(const WaveCtx<CAVITY>& x, const LexCtx& 
 // residual row per step for T = 1 .. 2NS, none otherwise). An iteration whose
 // sampled rows all meet the tolerance is left open (LexCtl::kexact, stop
 // code 2) and evaluated exactly by the host (Solver::solve_lexw).
-template <int MODE, int T, int X>
-constexpr bool lx_res_row() { return !(MODE & LX_SAMPLE) || T == X; }
+// From 5 sweeps on the sampled rows are j = Rbeg - (2NS - 8) - 10q, the rows
+// the 4-sweep launch samples for the same band end (a band ending at the top
+// ghost row then samples row ny at every depth: the first step of a run from
+// rest has its residual next to the lid, and a launch that samples no row
+// there leaves its first iterations open and runs the whole solve on the
+// exact kernels), i.e. X = T - (2NS - 8) modulo 10: every step of the unroll
+// has a residual row, steps with two are 10 rows apart.
+template <int MODE, int T, int X, int NS>
+constexpr bool lx_res_row() {
+  return !(MODE & LX_SAMPLE) || (NS >= 5 ? (X - T + 2 * NS - 8 + 20) % 10 == 0 : T == X);
+}
+// step T of the unroll evaluates a residual row
+template <int MODE, int T, int NS>
+constexpr bool lx_res_step() { return !(MODE & LX_SAMPLE) || NS >= 5 || (T >= 1 && T <= 2 * NS); }
 
 // column data of a wave: the cavity's wall kinds (LxCol) / the open cases' ghost kinds (LxoCol)
 template <int CASE>
@@ -661,44 +701,67 @@ struct LxCols {
   LxoCol oc;
 };
 
-template <int CASE, int S, int NS, int T, int ROT, int PAR, int MODE, bool EDGE, bool RC, bool UP = false>
+// source row R + X at step T of the unroll: ring position T + 9 - X (LX_S10; LR:
+// from the runtime base, modulo the LDS ring's depth)
+template <int T, int ROT, int PAR, int X, int NS, bool LR>
+__device__ __forceinline__ double2 lx_fr(const LexRun<NS, LR>& s) {
+  if constexpr (LR) {
+    constexpr int D = lexw_ring(NS);
+    return s.ring[((s.rb + (T + 9 - X + D)) & (D - 1)) * 64];
+  } else {
+    return s.fr[LX_S10(X)];
+  }
+}
+
+template <int CASE, int S, int NS, int T, int ROT, int PAR, int MODE, bool EDGE, bool RC, bool UP = false, bool LR = false>
 __device__ __forceinline__ void lx_sweeps(const WaveCtx<CAVITY>& x, const LexCtx& lc, const LexCtl& L,
-                                          const LxCols<CASE>& cl, LexRun<NS>& s, int R, const LxAct& act, int& exi) {
+                                          const LxCols<CASE>& cl, LexRun<NS, LR>& s, int R, const LxAct& act, int& exi,
+                                          double2 f1 = make_double2(0.0, 0.0), double2 f2 = make_double2(0.0, 0.0)) {
   if constexpr (S < NS) {
+    // (LDS ring: the next sweep's source rows are read a sweep ahead, their latency under this sweep's rows)
+    constexpr bool AH = LR && CFD_LEXW_LDS_AHEAD;
+    if constexpr (!AH || S == 0) f1 = lx_fr<T, ROT, PAR, 2 * S + 1>(s), f2 = lx_fr<T, ROT, PAR, 2 * S + 2>(s);
+    double2 g1 = f1, g2 = f2;
+    if constexpr (AH && S + 1 < NS) g1 = lx_fr<T, ROT, PAR, 2 * S + 3>(s), g2 = lx_fr<T, ROT, PAR, 2 * S + 4>(s);
     // red at R+2S+1 (parity PAR^1) in half-sweep H0+2S; black at R+2S+2 (PAR) in H0+2S+1
     // (UP: at R-2S-1, R-2S-2, the same parities)
     constexpr int D = UP ? -1 : 1;
     if constexpr (CASE == CAVITY) {
-      lx_row<ROT, PAR ^ 1, 0, MODE, EDGE, false, lx_res_row<MODE, T, 2 * S + 1>(), UP>(
-          x, lc, cl.cc, s.w[S], R + D * (2 * S + 1), 2 * S + 1, act, s.fr[LX_S10(2 * S + 1)], exi);
-      lx_row<ROT, PAR, 1, MODE, EDGE, S == NS - 1, lx_res_row<MODE, T, 2 * S + 2>(), UP>(
-          x, lc, cl.cc, s.w[S], R + D * (2 * S + 2), 2 * S + 2, act, s.fr[LX_S10(2 * S + 2)], exi);
+      lx_row<ROT, PAR ^ 1, 0, MODE, EDGE, false, lx_res_row<MODE, T, 2 * S + 1, NS>(), UP>(
+          x, lc, cl.cc, s.w[S], R + D * (2 * S + 1), 2 * S + 1, act, f1, exi);
+      lx_row<ROT, PAR, 1, MODE, EDGE, S == NS - 1, lx_res_row<MODE, T, 2 * S + 2, NS>(), UP>(
+          x, lc, cl.cc, s.w[S], R + D * (2 * S + 2), 2 * S + 2, act, f2, exi);
     } else {
-      lxo_row<CASE, ROT, PAR ^ 1, 0, MODE, EDGE, RC, false, lx_res_row<MODE, T, 2 * S + 1>(), S == 0, false, UP>(
-          x, lc, L, cl.oc, s.w[S], R + D * (2 * S + 1), 2 * S + 1, act, s.fr[LX_S10(2 * S + 1)], exi, s.d);
+      lxo_row<CASE, ROT, PAR ^ 1, 0, MODE, EDGE, RC, false, lx_res_row<MODE, T, 2 * S + 1, NS>(), S == 0, false, UP>(
+          x, lc, L, cl.oc, s.w[S], R + D * (2 * S + 1), 2 * S + 1, act, f1, exi, s.d);
       double2* nxt = nullptr;  // row R+2S+3 in the next sweep's ring (the step's corner write)
       if constexpr (S + 1 < NS && !UP) nxt = &s.w[S + 1][LX_SLOT(2 * S + 3)];
-      lxo_row<CASE, ROT, PAR, 1, MODE, EDGE, RC, S == NS - 1, lx_res_row<MODE, T, 2 * S + 2>(), false, S == NS - 1, UP>(
-          x, lc, L, cl.oc, s.w[S], R + D * (2 * S + 2), 2 * S + 2, act, s.fr[LX_S10(2 * S + 2)], exi, s.d, nxt);
+      lxo_row<CASE, ROT, PAR, 1, MODE, EDGE, RC, S == NS - 1, lx_res_row<MODE, T, 2 * S + 2, NS>(), false, S == NS - 1, UP>(
+          x, lc, L, cl.oc, s.w[S], R + D * (2 * S + 2), 2 * S + 2, act, f2, exi, s.d, nxt);
     }
     if constexpr (S + 1 < NS) s.w[S + 1][LX_SLOT(2 * S + 2)] = s.w[S][LX_SLOT(2 * S + 2)];
-    lx_sweeps<CASE, S + 1, NS, T, ROT, PAR, MODE, EDGE, RC, UP>(x, lc, L, cl, s, R, act, exi);
+    lx_sweeps<CASE, S + 1, NS, T, ROT, PAR, MODE, EDGE, RC, UP, LR>(x, lc, L, cl, s, R, act, exi, g1, g2);
   }
 }
 
-template <int CASE, int NS, int T, int ROT, int PAR, int MODE, bool EDGE, bool RC, bool UP = false>  // PAR = parity of R, T = step of the unroll
+template <int CASE, int NS, int T, int ROT, int PAR, int MODE, bool EDGE, bool RC, bool UP = false, bool LR = false>  // PAR = parity of R, T = step of the unroll
 __device__ __forceinline__ void lx_step(const WaveCtx<CAVITY>& x, const LexCtx& lc, const LexCtl& L,
-                                        const LxCols<CASE>& cl, LexRun<NS>& s, int R, unsigned long long bit) {
+                                        const LxCols<CASE>& cl, LexRun<NS, LR>& s, int R, unsigned long long bit) {
   constexpr int D = UP ? -1 : 1;
   s.w[0][LX_SLOT(0)] = s.np[LX_SLOT(0)];
-  s.fr[LX_S10(1)] = s.nf[LX_SLOT(0)];
+  if constexpr (LR) {
+    constexpr int RD = lexw_ring(NS);
+    s.ring[((s.rb + (T + 8 + RD)) & (RD - 1)) * 64] = s.nf[LX_SLOT(0)];
+  } else {
+    s.fr[LX_S10(1)] = s.nf[LX_SLOT(0)];
+  }
   s.np[LX_SLOT(-4)] = lx_ld(x, x.pin, R - 4 * D);
   s.nf[LX_SLOT(-4)] = lx_ld(x, x.f, R - 3 * D);
   int exi = 0;
   const LxAct act = lx_act<MODE, CASE == BACKSTEP && EDGE && RC>(lc, x.gi, R);
-  lx_sweeps<CASE, 0, NS, T, ROT, PAR, MODE, EDGE, RC, UP>(x, lc, L, cl, s, R, act, exi);
+  lx_sweeps<CASE, 0, NS, T, ROT, PAR, MODE, EDGE, RC, UP, LR>(x, lc, L, cl, s, R, act, exi);
   if constexpr (UP) return;  // (no residuals marching up)
-  if constexpr ((MODE & LX_SAMPLE) && (T < 1 || T > 2 * NS)) return;  // (no residual row at this step)
+  if constexpr (!lx_res_step<MODE, T, NS>()) return;  // (no residual row at this step)
   s.mask |= exi ? bit : 0ull;
 }
 
@@ -726,6 +789,13 @@ __device__ __forceinline__ void lexw_flush(const LexCtl& L, int sh, int q0, cons
   }
 }
 
+// the block's source-row rings (lexw_lds): 4 waves x lexw_ring(NS) slots x 64 lanes x 16 B
+template <int NS>
+__device__ __forceinline__ double2* lx_ring() {
+  __shared__ double2 ring[4 * lexw_ring(NS) * 64];
+  return ring;
+}
+
 // UP (the cavity's steady interior bands, lexw_updown): the same march
 // mirrored - the front row climbs from below the band, sweep S red at R-2S-1,
 // black at R-2S-2 - without residuals (a residual needs its row's south
@@ -743,14 +813,22 @@ __device__ __forceinline__ void lx_march(const WaveCtx<CAVITY>& x, const LexCtx&
   const int Rb0 = UP ? y0 - H : y1 - 1 + H;
   const int Rbeg = UP ? Rb0 - (Rb0 & 1) : Rb0 + (Rb0 & 1);  // even first front row: compile-time colours
   const int nsteps = (y1 - y0) + 2 * H + (Rb0 & 1);
-  LexRun<NS> s;
+  constexpr bool LR = lexw_lds(CASE, NS);
+  LexRun<NS, LR> s;
   const double2 z = make_double2(0.0, 0.0);
 #pragma unroll
   for (int k = 0; k < 5; ++k)
 #pragma unroll
     for (int q = 0; q < NS; ++q) s.w[q][k] = z;
+  if constexpr (LR) {
+    s.ring = lx_ring<NS>() + (threadIdx.x >> 6) * (lexw_ring(NS) * 64) + lane;
+    s.rb = 0;
 #pragma unroll
-  for (int k = 0; k < 10; ++k) s.fr[k] = z;
+    for (int k = 0; k < lexw_ring(NS); ++k) s.ring[k * 64] = z;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) s.fr[k] = z;
+  }
   {
     constexpr int ROT = 0;
 #pragma unroll
@@ -778,6 +856,7 @@ __device__ __forceinline__ void lx_march(const WaveCtx<CAVITY>& x, const LexCtx&
       lx_step<CASE, NS, 7, 2, 1, MODE, EDGE, RC, true>(x, lc, L, cl, s, R + 7, 0ull);
       lx_step<CASE, NS, 8, 3, 0, MODE, EDGE, RC, true>(x, lc, L, cl, s, R + 8, 0ull);
       lx_step<CASE, NS, 9, 4, 1, MODE, EDGE, RC, true>(x, lc, L, cl, s, R + 9, 0ull);
+      if constexpr (LR) s.rb = (s.rb + 10) & (lexw_ring(NS) - 1);
     }
     return;
   }
@@ -819,6 +898,7 @@ __device__ __forceinline__ void lx_march(const WaveCtx<CAVITY>& x, const LexCtx&
     lx_step<CASE, NS, 7, 2, 1, MODE, EDGE, RC>(x, lc, L, cl, s, R - 7, LX_BIT(7));
     lx_step<CASE, NS, 8, 3, 0, MODE, EDGE, RC>(x, lc, L, cl, s, R - 8, LX_BIT(8));
     lx_step<CASE, NS, 9, 4, 1, MODE, EDGE, RC>(x, lc, L, cl, s, R - 9, LX_BIT(9));
+    if constexpr (LR) s.rb = (s.rb + 10) & (lexw_ring(NS) - 1);
   }
 #undef LX_BIT
   // lane l's bit u <-> iteration Bd0 + u - l = (Bd0 - 63) + (u + 63 - l):

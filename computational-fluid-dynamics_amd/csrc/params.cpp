@@ -193,6 +193,20 @@ extern "C" int cfd_tuning_default(const cfd_params* p, int knob, int* value) {
   }
 }
 
+// Sweeps per reference-order launch on one strip when sweeps_per_launch is 0
+// (Solver::lexw_ns; strips and ranks keep 3). 4, except the cavity from
+// 4096^2 cells on: 5, with the source-row ring in LDS (lexw.hpp lexw_lds).
+// Measured on MI355X, cavity, cap 10000 (profiles/r7/lexw_deep/README.md):
+// 4096^2 221 ms per step at 4, 204-209 at 5, 207-209 at 6 (the 6-sweep launch
+// is VALU-bound: 106 us against 87 at 5); 2048^2 88-91 / 96 / 109 and 1024^2
+// 58 / 61 / 70 ms - there one resident round of waves leaves bands of ~20
+// rows, and the deeper pipeline's fill (4NS + 3 rows per band) costs more than
+// the launches it saves.
+int cfd::lexw_auto_sweeps(const cfd_params& p) {
+  const bool cav = p.case_id == CFD_CAVITY || p.case_id == CFD_RAYLEIGH_BENARD;
+  return (cav && (long long)p.nx * p.ny >= 4096LL * 4096LL) ? 5 : 4;
+}
+
 // ------------------------------------------------------------ multigrid --
 // The plan of the multigrid pressure solve (mg.hpp): level 0 is
 // the solver's grid; level l+1 (half the cells per direction) exists while

@@ -290,12 +290,22 @@ class Solver {
            (P.case_id == CFD_CAVITY || P.case_id == CFD_CHANNEL || (P.case_id == CFD_BACKSTEP && step_lexw_ok()));
   }
   double* cscr = nullptr;  // the step's deferred corner residual across launches (LexCtl::cscr)
-  // sweeps per reference-order launch: 4 (auto) on one strip; strips and
-  // ranks keep 3 (their 8-row halos serve up to 3, lexw.hpp lexw_twc); the
-  // cavity also 1-3
+  // sweeps per reference-order launch: auto on one strip is params.cpp's
+  // lexw_auto_sweeps (4; the cavity's large grids deeper); strips and ranks
+  // keep 3 (their 8-row halos serve up to 3, lexw.hpp lexw_twc); the cavity
+  // also 1-3, 5 and 6 when asked
   int lexw_ns() const {
-    const int ns = (P.case_id != CFD_CAVITY || P.sweeps_per_launch < 1) ? 4 : P.sweeps_per_launch;
+    const int ns = P.case_id != CFD_CAVITY ? 4 : P.sweeps_per_launch < 1 ? lexw_auto_sweeps(P) : P.sweeps_per_launch;
     return multi() ? std::min(ns, 3) : ns;
+  }
+  // blocks per CU that both the steady and the ramp instance of a
+  // reference-order launch fit (registers and static LDS)
+  template <int CASE, int NS, bool SAMPLE>
+  static int lexw_blocks() {
+    int a = 0, b = 0;
+    HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, poisson_lexw_kernel<CASE, NS, false, SAMPLE>, 256, 0));
+    HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, poisson_lexw_kernel<CASE, NS, true, SAMPLE>, 256, 0));
+    return std::min(a, b);
   }
   bool ranks() const { return comm && comm->nranks > 1; }
   // Reference order on ranks: the exceedance bits of the iterations every
@@ -422,19 +432,20 @@ class Solver {
       // bands: fewer halo rows), exact ones for 3 (measured at 4096^2, §4)
       if (P.case_id == CFD_CAVITY && proof_ok()) pps = std::min(pps, 2);
       if (use_lexw()) {
+        // one resident round of the kernels that run: the steady and the ramp
+        // instance of this (case, sweeps per launch), the smaller of the two
+        // (sampled residual rows from 3 sweeps on, the capped solve's launches;
+        // the LDS ring is static shared memory, so the query counts it)
+        const int ns = lexw_ns();
         int lps = 0;
-        if (P.case_id == CFD_CHANNEL)
-          HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&lps, poisson_lexw_kernel<CHANNEL, 4, false, true>, 256, 0));
-        else if (P.case_id == CFD_BACKSTEP)
-          HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&lps, poisson_lexw_kernel<BACKSTEP, 4, false, true>, 256, 0));
-        else if (lexw_ns() == 4)
-          HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&lps, poisson_lexw_kernel<CAVITY, 4, false, true>, 256, 0));
-        else if (lexw_ns() == 1)
-          HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&lps, poisson_lexw_kernel<CAVITY, 1, false>, 256, 0));
-        else if (lexw_ns() == 2)
-          HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&lps, poisson_lexw_kernel<CAVITY, 2, false>, 256, 0));
-        else
-          HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&lps, poisson_lexw_kernel<CAVITY, 3, false, true>, 256, 0));
+        if (P.case_id == CFD_CHANNEL) lps = ns == 3 ? lexw_blocks<CHANNEL, 3, true>() : lexw_blocks<CHANNEL, 4, true>();
+        else if (P.case_id == CFD_BACKSTEP) lps = ns == 3 ? lexw_blocks<BACKSTEP, 3, true>() : lexw_blocks<BACKSTEP, 4, true>();
+        else if (ns == 6) lps = lexw_blocks<CAVITY, 6, true>();
+        else if (ns == 5) lps = lexw_blocks<CAVITY, 5, true>();
+        else if (ns == 4) lps = lexw_blocks<CAVITY, 4, true>();
+        else if (ns == 1) lps = lexw_blocks<CAVITY, 1, false>();
+        else if (ns == 2) lps = lexw_blocks<CAVITY, 2, false>();
+        else lps = lexw_blocks<CAVITY, 3, true>();
         resident_lexw_waves = std::max(1, std::min(lps, 4)) * 4 * prop.multiProcessorCount;
       }
       resident_pair_waves = pps * 4 * prop.multiProcessorCount;
@@ -626,9 +637,21 @@ class Solver {
     if (!(P.omega > 0) || !(P.omega < 2)) throw Error(CFD_E_ARG, "SOR omega must lie in (0, 2)");
     if (P.max_iters < 0) throw Error(CFD_E_ARG, "max_iters must be >= 0");
     if (P.check_every < 1) throw Error(CFD_E_ARG, "check_every must be >= 1");
-    if (P.sweeps_per_launch < 0 || P.sweeps_per_launch > 5 ||
-        (P.sweeps_per_launch == 5 && !(P.ordering == CFD_ORDER_LEX && P.case_id == CFD_CAVITY)))
-      throw Error(CFD_E_ARG, "sweeps_per_launch must be 0 (auto), 1, 2, 3, 4 or 5 (the cavity's lexicographic order)");
+    if (P.sweeps_per_launch < 0 || P.sweeps_per_launch > 6 ||
+        (P.sweeps_per_launch >= 5 && !(P.ordering == CFD_ORDER_LEX && P.case_id == CFD_CAVITY)))
+      throw Error(CFD_E_ARG,
+                  "sweeps_per_launch must be 0 (auto), 1, 2, 3, 4 or 5, 6 (the cavity's lexicographic order)");
+    // 6 exists in the multi-block march only. Up to 5 the one-workgroup
+    // reference-order solve (smlex.hip) ignores the value; the new one is
+    // refused where that solve would take the grid, rather than ignored
+    if (P.sweeps_per_launch == 6 && P.small_solve != CFD_OFF && nstrips == 1 && !comm) {
+      Geo g{};
+      g.nx = P.nx;
+      g.ny = P.ny;
+      if (smlex_fits(g, make_coef(P)))
+        throw Error(CFD_E_ARG, "sweeps_per_launch 6 runs in the multi-block reference-order march: this grid goes to "
+                               "the one-workgroup solve (small_solve off selects the march)");
+    }
     if (P.sweeps_per_launch == 3 && P.case_id != CFD_CAVITY && P.ordering == CFD_ORDER_RB)
       throw Error(CFD_E_ARG, "three red-black sweeps per launch are implemented for the cavity only");
     if (P.sweeps_per_launch >= 1 && P.sweeps_per_launch != 4 && P.ordering == CFD_ORDER_LEX &&
@@ -1243,6 +1266,9 @@ class Solver {
     } else if (P.case_id == CFD_CHANNEL) {
       if (sample) { if (steady) CFD_LEXW_LAUNCH(CHANNEL, 4, false, true); else CFD_LEXW_LAUNCH(CHANNEL, 4, true, true); }
       else { if (steady) CFD_LEXW_LAUNCH(CHANNEL, 4, false, false); else CFD_LEXW_LAUNCH(CHANNEL, 4, true, false); }
+    } else if (ns == 6) {
+      if (sample) { if (steady) CFD_LEXW_LAUNCH(CAVITY, 6, false, true); else CFD_LEXW_LAUNCH(CAVITY, 6, true, true); }
+      else { if (steady) CFD_LEXW_LAUNCH(CAVITY, 6, false, false); else CFD_LEXW_LAUNCH(CAVITY, 6, true, false); }
     } else if (ns == 5) {
       if (sample) { if (steady) CFD_LEXW_LAUNCH(CAVITY, 5, false, true); else CFD_LEXW_LAUNCH(CAVITY, 5, true, true); }
       else { if (steady) CFD_LEXW_LAUNCH(CAVITY, 5, false, false); else CFD_LEXW_LAUNCH(CAVITY, 5, true, false); }
@@ -1282,7 +1308,9 @@ class Solver {
     std::vector<PairPlan> plans(S.size());
     for (size_t q = 0; q < S.size(); ++q)
       plans[q] = multi_plan(S[q].g.wj0, S[q].g.wj1 + 1, 0, 0, resident_lexw_waves / (int)S.size(), ns,
-                            ns >= 5 ? 90 : 96,  // (a wave's march steps + 9 <= 127: its iterations fit one 64-bit mask)
+                            // (a wave's march steps + 9 <= 127: its iterations fit one 64-bit
+                            // mask; at 6 sweeps 90 + 2 * 13 + 1 + 9 = 126)
+                            ns >= 5 ? 90 : 96,
                             lexw_edge_pct, lexw_twc(ns), lexw_extra(ns));
     // steady launches of strip q: every cell the strip's launch touches (its
     // rows and the HALO rows on each side: i + j in [smin, smax]) active in

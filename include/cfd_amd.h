@@ -77,10 +77,11 @@ typedef struct cfd_params {
   int sweeps_per_launch; /* SOR iterations fused into one kernel launch, bit-identical for every value:
                            0 = auto: red-black with the proof-mode test 4 (the backwards step on strips or
                            ranks: 3), red-black with exact residuals 3 (cavity) / 2 (channel, step);
-                           lexicographic order 4 (3 on strips); 1, 2; 3 (red-black: cavity only, every
-                           launch 3); 4 (red-black with the proof test, or the lexicographic order: the
-                           auto plan, stated); 5 (lexicographic cavity on one strip). Ignored by the
-                           one-workgroup solves (small_solve) */
+                           lexicographic order 4 (3 on strips; the cavity from 4096^2 cells on, one
+                           strip: 5); 1, 2; 3 (red-black: cavity only, every launch 3); 4 (red-black with
+                           the proof test, or the lexicographic order); 5, 6 (lexicographic cavity on one
+                           strip). Ignored by the one-workgroup solves (small_solve), except 6, which is
+                           refused where the one-workgroup reference-order solve would take the grid */
   /* Rayleigh-Benard (case 3), free-fall units: H = 1, U = sqrt(g beta dT H),
    * nu = sqrt(Pr/Ra), kappa = 1/sqrt(Ra Pr); hot bottom wall t_hot, cold top
    * wall t_cold, adiabatic side walls; buoyancy (T - t_ref) on v. */
