@@ -54,7 +54,8 @@ class _SolverBase:
         tuning: launch-planning knobs (_lib.TUNING names), performance only.
         poisson: "sor" (the reference's solve, the default) or "multigrid" (V-cycles to
         the reference's tolerance: the cavity and Rayleigh-Benard on one strip, no ranks;
-        see set_poisson_method). mg_options: pre_sweeps / post_sweeps / max_cycles."""
+        see set_poisson_method) or "multigrid-open" (the channel's multigrid solve, one
+        strip, no ranks). mg_options: pre_sweeps / post_sweeps / max_cycles."""
         self.params = params if params is not None else make_params(self.CASE)
         if self.params.case_id != self.CASE:
             raise ValueError(f"{type(self).__name__} needs case {CASE_NAMES[self.CASE]}")
@@ -89,7 +90,9 @@ class _SolverBase:
         V(pre_sweeps, post_sweeps) cycles (defaults 2, 2; at most max_cycles, default 50)
         until the reference's residual meets its tolerance; they then return (cycles,
         residual). "sor" switches back. Raises CfdError naming the rule for the channel,
-        the step, strips, ranks and grids without a plan (mg_plan)."""
+        the step, strips, ranks and grids without a plan (mg_plan). "multigrid-open" is
+        the channel's method (semi-coarsened levels, a warm start from the current p; the
+        cavity, Rayleigh-Benard and the step are refused; plans: mg_open_plan)."""
         if method not in _lib.POISSON:
             raise ValueError(f"poisson must be one of {sorted(_lib.POISSON)}, got {method!r}")
         opt = mg_options or {}
@@ -227,7 +230,7 @@ class _SolverBase:
         for k in range(1, total + 1):
             t = k * p.dt
             it, res = self.step()
-            cap = self._mg_max_cycles if self.poisson == "multigrid" else p.max_iters  # (cycles in the iteration column)
+            cap = self._mg_max_cycles if self.poisson in ("multigrid", "multigrid-open") else p.max_iters  # (cycles in the iteration column)
             if it >= cap:
                 print(warning_line(p.case_id, cap, res), file=err)
             if k % p.print_interval == 0 or k == total:
@@ -313,6 +316,15 @@ def mg_plan(params: CaseParams) -> tuple[int, int, int]:
     _lib.check(_lib.lib().cfd_mg_plan(ctypes.byref(cp), ctypes.byref(lv), ctypes.byref(cx), ctypes.byref(cy)),
                "cfd_mg_plan")
     return lv.value, cx.value, cy.value
+
+
+def mg_open_plan(params: CaseParams) -> list[tuple[int, int]]:
+    """cfd_mg_open_plan (host only): [(nx, ny)] of every level of the channel's multigrid
+    plan of these parameters; raises CfdError naming the rule where there is none."""
+    cp = to_cparams(params)
+    lv, ax, ay = ctypes.c_int(), (ctypes.c_int * 16)(), (ctypes.c_int * 16)()
+    _lib.check(_lib.lib().cfd_mg_open_plan(ctypes.byref(cp), ctypes.byref(lv), ax, ay), "cfd_mg_open_plan")
+    return [(ax[l], ay[l]) for l in range(lv.value)]
 
 
 def params_from_library_rb(ra: float, pr: float, nx: int = 0, ny: int = 0, dt: float = 0.0) -> _lib.CfdParams:

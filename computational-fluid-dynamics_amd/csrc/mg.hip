@@ -19,6 +19,10 @@
 // indicator products are real multiplies on boundary cells (0 * x keeps x's
 // sign, as in the reference); interior cells skip them (1 * x == x), the same
 // bits. The library builds with -ffp-contract=off: no fused multiply-adds.
+//
+// The second half of the file (mgo_*) is the channel's scheme: the same
+// launches with an anisotropic, semi-coarsened operator and a Dirichlet zero
+// in the east ghost column (tests/mg_open_reference.py).
 #include <hip/hip_runtime.h>
 
 #include "mg.hpp"
@@ -336,7 +340,339 @@ __global__ __launch_bounds__(MG_TAIL_THREADS) void mg_tail_kernel(const MgLevel*
   }
 }
 
+// ============================================================ the channel ==
+// The second scheme (mg.hpp "the channel", tests/mg_open_reference.py): the
+// same streams and the same tile, halo and tail schemes with the anisotropic
+// cell functions below. A neighbour a cell does not have is skipped by a
+// select on the cell's mask (bit set: the neighbour exists), never multiplied
+// by 0, so the ghost cells - which hold the reference's refreshed values at
+// level 0 and nothing in particular elsewhere - reach no result.
+
+__device__ __forceinline__ int mgo_mask(const MgoLevel* L, int j, int i) {
+  return (int)(i > 1) | (int)(i < L->nx) << 1 | (int)(j > 1) << 2 | (int)(j < L->ny) << 3;
+}
+
+// (cx pE + cx pW) + (cy pN + cy pS) over the neighbours that exist (the east zero of column nx adds nothing)
+__device__ __forceinline__ double mgo_sum(const MgoLevel* L, int k, double pW, double pE, double pS, double pN) {
+  const double tE = (k & 2) ? L->cx * pE : 0.0;
+  const double tW = (k & 1) ? L->cx * pW : 0.0;
+  const double tN = (k & 8) ? L->cy * pN : 0.0;
+  const double tS = (k & 4) ? L->cy * pS : 0.0;
+  return (tE + tW) + (tN + tS);
+}
+
+// Gauss-Seidel update of cell (j, i): rdiag (sum - f)
+__device__ __forceinline__ double mgo_relax(const MgoLevel* L, int j, int i, double pW, double pE, double pS, double pN,
+                                            double f) {
+  const int k = mgo_mask(L, j, i);
+  return L->rdiag[k] * (mgo_sum(L, k, pW, pE, pS, pN) - f);
+}
+
+// SOR update of the coarsest level: p (1 - w) + (w rdiag) (sum - f)
+__device__ __forceinline__ double mgo_sor(const MgoLevel* L, int j, int i, double pc, double pW, double pE, double pS,
+                                          double pN, double f) {
+  const int k = mgo_mask(L, j, i);
+  return pc * L->one_m_omega + L->omr[k] * (mgo_sum(L, k, pW, pE, pS, pN) - f);
+}
+
+// residual (cx (pE - c) + cx (pW - c)) + (cy (pN - c) + cy (pS - c)) - f; column nx: cE (0 - c) for its east term
+__device__ __forceinline__ double mgo_resid(const MgoLevel* L, int j, int i, double c, double pW, double pE, double pS,
+                                            double pN, double f) {
+  const int k = mgo_mask(L, j, i);
+  const double tE = (k & 2) ? L->cx * (pE - c) : L->cE * (0.0 - c);
+  const double tW = (k & 1) ? L->cx * (pW - c) : 0.0;
+  const double tN = (k & 8) ? L->cy * (pN - c) : 0.0;
+  const double tS = (k & 4) ? L->cy * (pS - c) : 0.0;
+  return ((tE + tW) + (tN + tS)) - f;
+}
+
+// residual of fine cell (j, i) from a field with rows of P doubles (global memory or LDS)
+__device__ __forceinline__ double mgo_resid_at(const MgoLevel* Lf, const double* p, const double* f, size_t P, int j,
+                                               int i) {
+  const size_t o = (size_t)j * P + i;
+  return mgo_resid(Lf, j, i, p[o], p[o - 1], p[o + 1], p[o - P], p[o + P], f[o]);
+}
+
+// Coarse source of cell (J, I): minus the mean of the residual over its children - four
+// (-1/4 ((rSW + rSE) + (rNW + rNE))), or two along the halved direction (-1/2 (rW + rE), -1/2 (rS + rN)).
+__device__ __forceinline__ double mgo_restrict_cell(const MgoLevel* Lf, const double* p, const double* f, size_t P, int J,
+                                                    int I) {
+  if (Lf->kind == MGO_X) {
+    const double rW = mgo_resid_at(Lf, p, f, P, J, 2 * I - 1), rE = mgo_resid_at(Lf, p, f, P, J, 2 * I);
+    return -0.5 * (rW + rE);
+  }
+  if (Lf->kind == MGO_Y) {
+    const double rS = mgo_resid_at(Lf, p, f, P, 2 * J - 1, I), rN = mgo_resid_at(Lf, p, f, P, 2 * J, I);
+    return -0.5 * (rS + rN);
+  }
+  const int j = 2 * J - 1, i = 2 * I - 1;
+  const double rSW = mgo_resid_at(Lf, p, f, P, j, i), rSE = mgo_resid_at(Lf, p, f, P, j, i + 1);
+  const double rNW = mgo_resid_at(Lf, p, f, P, j + 1, i), rNE = mgo_resid_at(Lf, p, f, P, j + 1, i + 1);
+  return -0.25 * ((rSW + rSE) + (rNW + rNE));
+}
+
+// e of the coarse level with one ghost layer: south / north ghosts = rows 1 / ny, then
+// the west ghost = column 1 and the east ghost = column nx times g (the line through the zero).
+__device__ __forceinline__ double mgo_ext(const MgoLevel* Lc, const double* e, int pitch, int J, int I) {
+  const int jj = min(max(J, 1), Lc->ny);
+  if (I == 0) return e[(size_t)jj * pitch + 1];
+  if (I == Lc->nx + 1) return e[(size_t)jj * pitch + Lc->nx] * Lc->g;
+  return e[(size_t)jj * pitch + I];
+}
+
+// correction of fine cell (j, i): bilinear (((9 c + 3 V) + 3 H) + D) / 16, or linear along the
+// halved direction, (3 c + H) / 4 or (3 c + V) / 4; V / H / D the coarse neighbours on the child's side
+__device__ __forceinline__ double mgo_corr(const MgoLevel* Lc, int kind, const double* e, int pitch, int j, int i) {
+  const int dj = (j & 1) ? -1 : 1, di = (i & 1) ? -1 : 1;
+  if (kind == MGO_X) {
+    const int I = (i + 1) >> 1;
+    return (3.0 * e[(size_t)j * pitch + I] + mgo_ext(Lc, e, pitch, j, I + di)) * 0.25;
+  }
+  if (kind == MGO_Y) {
+    const int J = (j + 1) >> 1;
+    return (3.0 * e[(size_t)J * pitch + i] + mgo_ext(Lc, e, pitch, J + dj, i)) * 0.25;
+  }
+  const int J = (j + 1) >> 1, I = (i + 1) >> 1;
+  const double c = e[(size_t)J * pitch + I];
+  const double V = mgo_ext(Lc, e, pitch, J + dj, I);
+  const double H = mgo_ext(Lc, e, pitch, J, I + di);
+  const double D = mgo_ext(Lc, e, pitch, J + dj, I + di);
+  return (((9.0 * c + 3.0 * V) + 3.0 * H) + D) * 0.0625;
+}
+
+// One colour of a sweep of level l (mg_smooth_kernel's layout). Block: 4 waves = 4 rows x 128 columns.
+__global__ __launch_bounds__(256) void mgo_smooth_kernel(const MgoLevel* __restrict__ lv, int l, double* p,
+                                                         const double* __restrict__ f, int colour) {
+  const MgoLevel* L = lv + l;
+  const int nx = L->nx, ny = L->ny;
+  const int lane = threadIdx.x & 63;
+  const int gi = blockIdx.x * 128 + 2 * lane;  // even: a 16-B aligned pair
+  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j > ny || gi > nx) return;
+  const int t = (j + colour) & 1;  // colour 0 holds the cells with i + j even: component t of the pair
+  const int i = gi + t;
+  if (i < 1 || i > nx) return;
+  const size_t P = (size_t)L->pitch, o = (size_t)j * P + gi;
+  const double2 pc = *reinterpret_cast<const double2*>(p + o);
+  const double2 ps = *reinterpret_cast<const double2*>(p + o - P);
+  const double2 pn = *reinterpret_cast<const double2*>(p + o + P);
+  const double2 fc = *reinterpret_cast<const double2*>(f + o);
+  double v;
+  if (t == 0) v = mgo_relax(L, j, i, p[o - 1], pc.y, ps.x, pn.x, fc.x);  // (i >= 2: o - 1 is column i - 1 >= 1)
+  else v = mgo_relax(L, j, i, pc.x, p[o + 2], ps.y, pn.y, fc.y);        // (o + 2: column i + 1 <= nx + 1 < pitch)
+  p[o + t] = v;
+}
+
+// nsw (1..3) whole sweeps of level l in one launch, pin -> pout: mg_smooth_tile_kernel's
+// tile (64 rows x 128 columns of p in LDS, 64 KiB), halo scheme and ownership, with the
+// channel's cell function. Cells outside rows 0 .. ny+1 / columns 0 .. nx+1 are loaded as 0
+// and, like the ghost cells, never selected.
+__global__ __launch_bounds__(MG_TILE_THREADS) void mgo_smooth_tile_kernel(const MgoLevel* __restrict__ lv, int l,
+                                                                          const double* __restrict__ pin,
+                                                                          double* __restrict__ pout,
+                                                                          const double* __restrict__ f, int nsw) {
+  __shared__ double S[MG_TR * MG_TC];
+  const MgoLevel* L = lv + l;
+  const int nx = L->nx, ny = L->ny;
+  const int H = 2 * nsw, TW = MG_TC - 2 * H, TH = MG_TR - 2 * H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c0 = 2 * lane;
+  const int gx = (int)blockIdx.x * TW - H + c0;  // even (or negative: outside)
+  const int gy0 = (int)blockIdx.y * TH - H;
+  const size_t P = (size_t)L->pitch;
+  const bool colin = gx >= 0 && gx <= nx + 1;  // (gx + 1 <= nx + 2 < pitch)
+  double2 fr[MG_TQ];
+#pragma unroll
+  for (int q = 0; q < MG_TQ; ++q) {
+    const int r = w + 16 * q, gy = gy0 + r;
+    double2 v = make_double2(0.0, 0.0);
+    fr[q] = v;
+    if (colin && gy >= 0 && gy <= ny + 1) {
+      v = *reinterpret_cast<const double2*>(pin + (size_t)gy * P + gx);
+      fr[q] = *reinterpret_cast<const double2*>(f + (size_t)gy * P + gx);
+    }
+    *reinterpret_cast<double2*>(&S[r * MG_TC + c0]) = v;
+  }
+  __syncthreads();
+  for (int k = 0; k < 2 * nsw; ++k) {
+#pragma unroll
+    for (int q = 0; q < MG_TQ; ++q) {
+      const int r = w + 16 * q, gy = gy0 + r;
+      const int t = (gy + k) & 1;  // colour k & 1: the cells with i + j + colour even (gx is even)
+      const int c = c0 + t, i = gx + t;
+      if (r > k && r < MG_TR - 1 - k && c > k && c < MG_TC - 1 - k && gy >= 1 && gy <= ny && i >= 1 && i <= nx) {
+        const int o = r * MG_TC + c;
+        S[o] = mgo_relax(L, gy, i, S[o - 1], S[o + 1], S[o - MG_TC], S[o + MG_TC], t ? fr[q].y : fr[q].x);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < MG_TQ; ++q) {
+    const int r = w + 16 * q, gy = gy0 + r;
+    if (r < H || r >= H + TH || c0 < H || c0 >= H + TW || gy < 1 || gy > ny) continue;  // (H, TW even: a pair is owned whole)
+    const double2 v = *reinterpret_cast<const double2*>(&S[r * MG_TC + c0]);
+    double* o = pout + (size_t)gy * P + gx;
+    if (gx >= 1 && gx + 1 <= nx) *reinterpret_cast<double2*>(o) = v;
+    else if (gx >= 1 && gx <= nx) o[0] = v.x;
+    else if (gx + 1 >= 1 && gx + 1 <= nx) o[1] = v.y;
+  }
+}
+
+// Residual of level l + restriction to level l + 1 by level l's kind; e_{l+1} = 0.
+// One thread per coarse cell; block: 4 coarse rows x 64 coarse columns.
+__global__ __launch_bounds__(256) void mgo_restrict_kernel(const MgoLevel* __restrict__ lv, int l,
+                                                           const double* __restrict__ p, const double* __restrict__ f,
+                                                           double* __restrict__ fc, double* __restrict__ ec) {
+  const MgoLevel* Lf = lv + l;
+  const MgoLevel* Lc = lv + l + 1;
+  const int I = 1 + blockIdx.x * 64 + (threadIdx.x & 63);
+  const int J = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (I > Lc->nx || J > Lc->ny) return;
+  const size_t oc = (size_t)J * Lc->pitch + I;
+  fc[oc] = mgo_restrict_cell(Lf, p, f, (size_t)Lf->pitch, J, I);
+  ec[oc] = 0.0;
+}
+
+// p_l += interpolant of e_{l+1}. Block: 4 rows x 128 columns, a lane one aligned pair.
+__global__ __launch_bounds__(256) void mgo_prolong_kernel(const MgoLevel* __restrict__ lv, int l, double* __restrict__ p,
+                                                          const double* __restrict__ ec) {
+  const MgoLevel* L = lv + l;
+  const MgoLevel* Lc = lv + l + 1;
+  const int nx = L->nx, ny = L->ny, kind = L->kind;
+  const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
+  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j > ny || gi > nx) return;
+  const size_t o = (size_t)j * L->pitch + gi;
+  const int pc = Lc->pitch;
+  if (gi >= 1 && gi + 1 <= nx) {
+    double2 v = *reinterpret_cast<const double2*>(p + o);
+    v.x += mgo_corr(Lc, kind, ec, pc, j, gi);
+    v.y += mgo_corr(Lc, kind, ec, pc, j, gi + 1);
+    *reinterpret_cast<double2*>(p + o) = v;
+  } else if (gi >= 1) {
+    p[o] += mgo_corr(Lc, kind, ec, pc, j, gi);  // (gi == nx)
+  } else {
+    p[o + 1] += mgo_corr(Lc, kind, ec, pc, j, 1);  // (gi == 0; nx >= 2)
+  }
+}
+
+// one colour of a sweep of a level held in LDS (rows of nx + 2), by the whole workgroup
+__device__ __forceinline__ void mgo_tail_half_sweep(const MgoLevel* L, double* p, const double* f, int colour, bool sor) {
+  const int nx = L->nx, ny = L->ny, pitch = nx + 2, hw = (nx + 1) >> 1;
+  for (int q = threadIdx.x; q < ny * hw; q += MG_TAIL_THREADS) {
+    const int j = 1 + q / hw;
+    const int i = 1 + ((j + 1 + colour) & 1) + 2 * (q % hw);
+    if (i > nx) continue;
+    const int o = j * pitch + i;
+    p[o] = sor ? mgo_sor(L, j, i, p[o], p[o - 1], p[o + 1], p[o - pitch], p[o + pitch], f[o])
+               : mgo_relax(L, j, i, p[o - 1], p[o + 1], p[o - pitch], p[o + pitch], f[o]);
+  }
+  __syncthreads();
+}
+
+// The sub-cycle over levels l0 .. last in one workgroup (mg_tail_kernel's scheme), each
+// transfer by its fine level's kind.
+__global__ __launch_bounds__(MG_TAIL_THREADS) void mgo_tail_kernel(const MgoLevel* __restrict__ lv, int l0, int last,
+                                                                   int nu1, int nu2, const double* __restrict__ fg,
+                                                                   double* __restrict__ eg) {
+  __shared__ double S[MG_LDS_DOUBLES];
+  const int tid = threadIdx.x;
+  // every level's correction starts from zero, ghosts included
+  for (int l = l0; l <= last; ++l) {
+    const MgoLevel* L = lv + l;
+    const int n = (L->nx + 2) * (L->ny + 2);
+    for (int q = tid; q < n; q += MG_TAIL_THREADS) S[L->lds_p + q] = 0.0;
+  }
+  {
+    const MgoLevel* L = lv + l0;
+    const int nx = L->nx;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      S[L->lds_f + j * (nx + 2) + i] = fg[(size_t)j * L->pitch + i];
+    }
+  }
+  __syncthreads();
+  for (int l = l0; l < last; ++l) {
+    const MgoLevel* L = lv + l;
+    const MgoLevel* Lc = L + 1;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    for (int s = 0; s < nu1; ++s) {
+      mgo_tail_half_sweep(L, p, f, 0, false);
+      mgo_tail_half_sweep(L, p, f, 1, false);
+    }
+    const int ncx = Lc->nx, pcp = ncx + 2;
+    for (int q = tid; q < ncx * Lc->ny; q += MG_TAIL_THREADS) {
+      const int J = 1 + q / ncx, I = 1 + q % ncx;
+      S[Lc->lds_f + J * pcp + I] = mgo_restrict_cell(L, p, f, (size_t)(L->nx + 2), J, I);
+    }
+    __syncthreads();
+  }
+  {
+    const MgoLevel* L = lv + last;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    for (int s = 0; s < L->coarse_sweeps; ++s) {
+      mgo_tail_half_sweep(L, p, f, 0, true);
+      mgo_tail_half_sweep(L, p, f, 1, true);
+    }
+  }
+  for (int l = last - 1; l >= l0; --l) {
+    const MgoLevel* L = lv + l;
+    const MgoLevel* Lc = L + 1;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    const double* e = S + Lc->lds_p;
+    const int nx = L->nx, pf = nx + 2, kind = L->kind;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      p[j * pf + i] += mgo_corr(Lc, kind, e, Lc->nx + 2, j, i);
+    }
+    __syncthreads();
+    for (int s = 0; s < nu2; ++s) {
+      mgo_tail_half_sweep(L, p, f, 0, false);
+      mgo_tail_half_sweep(L, p, f, 1, false);
+    }
+  }
+  {
+    const MgoLevel* L = lv + l0;
+    const int nx = L->nx;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      eg[(size_t)j * L->pitch + i] = S[L->lds_p + j * (nx + 2) + i];
+    }
+  }
+}
+
 }  // namespace
+
+void mgo_smooth_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* f, int colour, void* stream) {
+  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
+  mgo_smooth_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, colour);
+}
+
+void mgo_smooth_tile_launch(const MgoLevel* dlv, const MgoLevel& L, int l, const double* pin, double* pout,
+                            const double* f, int nsw, void* stream) {
+  const int H = 2 * nsw;
+  const dim3 grid(L.nx / (MG_TC - 2 * H) + 1, L.ny / (MG_TR - 2 * H) + 1);
+  mgo_smooth_tile_kernel<<<grid, MG_TILE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, pin, pout, f, nsw);
+}
+
+void mgo_restrict_launch(const MgoLevel* dlv, const MgoLevel& Lc, int l, const double* p,
+                         const double* f, double* fc, double* ec, void* stream) {
+  const dim3 grid((Lc.nx + 63) / 64, (Lc.ny + 3) / 4);
+  mgo_restrict_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, fc, ec);
+}
+
+void mgo_prolong_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* ec, void* stream) {
+  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
+  mgo_prolong_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, ec);
+}
+
+void mgo_tail_launch(const MgoLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream) {
+  mgo_tail_kernel<<<1, MG_TAIL_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l0, last, nu1, nu2, fg, eg);
+}
 
 void mg_smooth_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* f, int colour, void* stream) {
   const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);

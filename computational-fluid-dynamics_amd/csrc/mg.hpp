@@ -67,4 +67,47 @@ void mg_prolong_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, c
 // f_{l0} read from fg, the correction e_{l0} written to eg.
 void mg_tail_launch(const MgLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
 
+// ------------------------------------------------------------- the channel --
+// The second scheme (CFD_POISSON_MULTIGRID_OPEN, DESIGN.md §8 "The channel"):
+// dx != dy, Neumann west / south / north and a Dirichlet zero in the east ghost
+// column (channel-01.cpp:642-688). Level l has spacings 2^a dx and 2^b dy, cx =
+// 1 / hx^2, cy = 1 / hy^2; column nx sees the zero d = 0.5 + 0.5^(a+1) spacings
+// away: east coefficient cE = cx / d with neighbour value 0. Levels are
+// semi-coarsened: with r = (hy / hx)^2, r > 2 halves x only, r < 1/2 y only,
+// otherwise both. Absent neighbours are skipped by selects, so no ghost cell's
+// value reaches a result. tests/mg_open_reference.py states every operation.
+enum { MGO_FULL = 0, MGO_X = 1, MGO_Y = 2 };
+
+struct MgoLevel {
+  int nx, ny;        // interior cells
+  int pitch;         // global memory: cell (j, i) at j * pitch + i (128-B aligned rows)
+  int lds_p, lds_f;  // one-launch tail: offsets (doubles) of p and f in LDS, rows of nx + 2 (-1: not in the tail)
+  int coarse_sweeps; // 4 max(nx, ny): SOR sweeps when this level is the coarsest
+  int kind;          // how this level is coarsened to the next: MGO_FULL / MGO_X / MGO_Y (-1: the coarsest)
+  int a, b;          // halvings of x and y down to this level
+  double cx, cy;     // 1 / hx^2, 1 / hy^2
+  double cE, g;      // east coefficient of column nx (cx / d); east ghost factor 1 - 1 / d of the prolongation
+  double rdiag[16];  // 1 / ((cw + ce) + (cs + cn)), index w | e << 1 | s << 2 | n << 3 (a set bit: that neighbour exists)
+  double one_m_omega;  // coarsest SOR: 1 - omega_c, omega_c = 2 / (1 + sin(pi / (max(nx, ny) + 1)))
+  double omr[16];      // omega_c * rdiag
+};
+
+struct MgoPlan {
+  int levels = 0;
+  int tail = 0;  // levels tail .. levels-1 run as one launch (tail >= 1)
+  MgoLevel lv[MG_MAX_LEVELS];
+};
+
+// The channel's plan of a parameter block, or false with the rule that refused it in `why` (host only: params.cpp).
+bool mgo_make_plan(const cfd_params& p, MgoPlan& plan, std::string& why);
+
+// Launches (mg.hip), as the cavity scheme's. The transfers read the kind from level l.
+void mgo_smooth_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* f, int colour, void* stream);
+void mgo_smooth_tile_launch(const MgoLevel* dlv, const MgoLevel& L, int l, const double* pin, double* pout,
+                            const double* f, int nsw, void* stream);
+void mgo_restrict_launch(const MgoLevel* dlv, const MgoLevel& Lc, int l, const double* p,
+                         const double* f, double* fc, double* ec, void* stream);
+void mgo_prolong_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* ec, void* stream);
+void mgo_tail_launch(const MgoLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
+
 }  // namespace cfd

@@ -1703,6 +1703,10 @@ class Solver {
   int mg_nu1 = 2, mg_nu2 = 2, mg_max_cycles = 50;
   cfd_mg_info mgi{};
   hipEvent_t mg_ev[4] = {};             // around the level-0 launches of a cycle's way down / way up
+  // CFD_POISSON_MULTIGRID_OPEN, the channel's scheme: its own plan and kernels (mgo_*), the buffers above
+  bool mgo_on = false;
+  MgoPlan mgop;
+  MgoLevel* mgo_dlv = nullptr;
 
   void mg_release() noexcept {
     for (double* q : mg_p)
@@ -1719,6 +1723,9 @@ class Solver {
     mg_cur.clear();
     if (mg_dlv) (void)hipFree(mg_dlv);
     mg_dlv = nullptr;
+    if (mgo_dlv) (void)hipFree(mgo_dlv);
+    mgo_dlv = nullptr;
+    mgo_on = false;
     for (auto& e : mg_ev) {
       if (e) (void)hipEventDestroy(e);
       e = nullptr;
@@ -1733,7 +1740,8 @@ class Solver {
       mgi.levels = mgi.coarse_nx = mgi.coarse_ny = mgi.coarse_sweeps = 0;
       return;
     }
-    if (method != CFD_POISSON_MULTIGRID) throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
+    const bool open = method == CFD_POISSON_MULTIGRID_OPEN;  // the channel's scheme (mg.hpp "the channel")
+    if (method != CFD_POISSON_MULTIGRID && !open) throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
     if (S.size() != 1) throw Error(CFD_E_ARG, "multigrid runs on one strip (strip rule): this solver has n_strips > 1");
     if (comm) throw Error(CFD_E_ARG, "multigrid runs without ranks (rank rule): this is a rank solver");
     const int nu1 = opt && opt->pre_sweeps ? opt->pre_sweeps : 2, nu2 = opt && opt->post_sweeps ? opt->post_sweeps : 2;
@@ -1741,18 +1749,31 @@ class Solver {
     if (nu1 < 0 || nu2 < 0 || nu1 + nu2 < 1 || mc < 1)
       throw Error(CFD_E_ARG, "multigrid options: sweeps must be >= 0 with at least one per cycle, max_cycles >= 1");
     MgPlan plan;
+    MgoPlan oplan;
     std::string why;
-    if (!mg_make_plan(P, plan, why)) throw Error(CFD_E_ARG, why);
-    if (plan.lv[0].pitch != pitch) throw Error(CFD_E_STATE, "multigrid plan pitch differs from the solver's");
+    if (open ? !mgo_make_plan(P, oplan, why) : !mg_make_plan(P, plan, why)) throw Error(CFD_E_ARG, why);
+    if ((open ? oplan.lv[0].pitch : plan.lv[0].pitch) != pitch)
+      throw Error(CFD_E_STATE, "multigrid plan pitch differs from the solver's");
+    const int levels = open ? oplan.levels : plan.levels, tail = open ? oplan.tail : plan.tail;
+    auto level_bytes = [&](int l) {
+      return open ? (size_t)(oplan.lv[l].ny + 2) * oplan.lv[l].pitch * sizeof(double)
+                  : (size_t)(plan.lv[l].ny + 2) * plan.lv[l].pitch * sizeof(double);
+    };
     HIPC(hipStreamSynchronize(st));
     mg_release();
-    mgp = plan;
-    HIPC(hipMalloc(&mg_dlv, sizeof(MgLevel) * MG_MAX_LEVELS));
-    HIPC(hipMemcpy(mg_dlv, mgp.lv, sizeof(MgLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
-    mg_p.assign(mgp.levels, nullptr);
-    mg_f.assign(mgp.levels, nullptr);
-    for (int l = 1; l <= mgp.tail; ++l) {  // (levels below the tail's first live in LDS only)
-      const size_t n = (size_t)(mgp.lv[l].ny + 2) * mgp.lv[l].pitch * sizeof(double);
+    if (open) {
+      mgop = oplan;
+      HIPC(hipMalloc(&mgo_dlv, sizeof(MgoLevel) * MG_MAX_LEVELS));
+      HIPC(hipMemcpy(mgo_dlv, mgop.lv, sizeof(MgoLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
+    } else {
+      mgp = plan;
+      HIPC(hipMalloc(&mg_dlv, sizeof(MgLevel) * MG_MAX_LEVELS));
+      HIPC(hipMemcpy(mg_dlv, mgp.lv, sizeof(MgLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
+    }
+    mg_p.assign(levels, nullptr);
+    mg_f.assign(levels, nullptr);
+    for (int l = 1; l <= tail; ++l) {  // (levels below the tail's first live in LDS only)
+      const size_t n = level_bytes(l);
       HIPC(hipMalloc(&mg_p[l], n));
       HIPC(hipMalloc(&mg_f[l], n));
       HIPC(hipMemsetAsync(mg_p[l], 0, n, st));  // ghost cells stay zero: no launch writes them
@@ -1760,15 +1781,15 @@ class Solver {
     }
     const char* fe = std::getenv("CFD_MG_FUSED");
     mg_fused = !(fe && fe[0] == '0');
-    mg_q.assign(mgp.levels, nullptr);
-    mg_cur.assign(mgp.levels, nullptr);
+    mg_q.assign(levels, nullptr);
+    mg_cur.assign(levels, nullptr);
     if (mg_fused) {
       const size_t n0 = (size_t)S[0].g.nrows * pitch * sizeof(double);
       HIPC(hipMalloc(&mg_q0, n0));
       HIPC(hipMemsetAsync(mg_q0, 0, n0, st));  // (its ghost cells stay zero, like p's)
       mg_q[0] = mg_q0 + (size_t)(0 - S[0].g.row_lo) * pitch;
-      for (int l = 1; l < mgp.tail; ++l) {
-        const size_t n = (size_t)(mgp.lv[l].ny + 2) * mgp.lv[l].pitch * sizeof(double);
+      for (int l = 1; l < tail; ++l) {
+        const size_t n = level_bytes(l);
         HIPC(hipMalloc(&mg_q[l], n));
         HIPC(hipMemsetAsync(mg_q[l], 0, n, st));
       }
@@ -1777,12 +1798,11 @@ class Solver {
     mg_nu1 = nu1;
     mg_nu2 = nu2;
     mg_max_cycles = mc;
-    const MgLevel& C = mgp.lv[mgp.levels - 1];
-    mgi.levels = mgp.levels;
-    mgi.coarse_nx = C.nx;
-    mgi.coarse_ny = C.ny;
-    mgi.coarse_sweeps = C.coarse_sweeps;
-    mg_on = true;
+    mgi.levels = levels;
+    mgi.coarse_nx = open ? oplan.lv[levels - 1].nx : plan.lv[levels - 1].nx;
+    mgi.coarse_ny = open ? oplan.lv[levels - 1].ny : plan.lv[levels - 1].ny;
+    mgi.coarse_sweeps = open ? oplan.lv[levels - 1].coarse_sweeps : plan.lv[levels - 1].coarse_sweeps;
+    (open ? mgo_on : mg_on) = true;
   }
 
   // one V-cycle from level 0 on mg_cur[0] (p0: row 0 of the solver's p buffer) / f0; returns its launches
@@ -1898,7 +1918,128 @@ class Solver {
     }
   }
 
+  // The channel's V-cycle (mg_vcycle with the mgo_* launches; each transfer's kind is level l's).
+  int mgo_vcycle(double* p0, const double* f0) {
+    int launches = 0;
+    auto F_ = [&](int l) { return l == 0 ? f0 : (const double*)mg_f[l]; };
+    auto smooth = [&](int l, int n) {
+      if (mg_fused) {  // up to 3 sweeps per launch, into the level's other buffer
+        for (int left = n; left > 0;) {
+          const int k = left == 4 ? 2 : std::min(left, 3);
+          double* a = l == 0 ? p0 : mg_p[l];
+          double* other = mg_cur[l] == a ? mg_q[l] : a;
+          mgo_smooth_tile_launch(mgo_dlv, mgop.lv[l], l, mg_cur[l], other, F_(l), k, st);
+          check_launch("mgo_smooth_tile");
+          ++launches;
+          mg_cur[l] = other;
+          left -= k;
+        }
+        return;
+      }
+      for (int q = 0; q < n; ++q)
+        for (int colour = 0; colour < 2; ++colour) {
+          mgo_smooth_launch(mgo_dlv, mgop.lv[l], l, mg_cur[l], F_(l), colour, st);
+          check_launch("mgo_smooth");
+          ++launches;
+        }
+    };
+    const int tail = mgop.tail, last = mgop.levels - 1;
+    HIPC(hipEventRecord(mg_ev[0], st));
+    for (int l = 0; l < tail; ++l) {
+      smooth(l, mg_nu1);
+      mg_cur[l + 1] = mg_p[l + 1];
+      mgo_restrict_launch(mgo_dlv, mgop.lv[l + 1], l, mg_cur[l], F_(l), mg_f[l + 1], mg_p[l + 1], st);
+      check_launch("mgo_restrict");
+      ++launches;
+      if (l == 0) HIPC(hipEventRecord(mg_ev[1], st));
+    }
+    mgo_tail_launch(mgo_dlv, tail, last, mg_nu1, mg_nu2, mg_f[tail], mg_p[tail], st);
+    check_launch("mgo_tail");
+    ++launches;
+    for (int l = tail - 1; l >= 0; --l) {
+      if (l == 0) HIPC(hipEventRecord(mg_ev[2], st));
+      mgo_prolong_launch(mgo_dlv, mgop.lv[l], l, mg_cur[l], mg_cur[l + 1], st);
+      check_launch("mgo_prolong");
+      ++launches;
+      smooth(l, mg_nu2);
+    }
+    HIPC(hipEventRecord(mg_ev[3], st));
+    return launches;
+  }
+
+  // The channel's solve (channel-01.cpp:642-688 with a V-cycle for the sweep): a warm start from the
+  // field the solver holds, the loop primed with tol + 1, after each cycle the reference's ghost
+  // refresh and its own max-norm residual on those ghosts.
+  void solve_mg_open(cfd_step_info* out) {
+    Strip& s = S[0];
+    double* X = s.b[pbuf(pcur)];
+    solve_tolerance();
+    const double tol = tol_host();
+    double* p0 = X + (size_t)(0 - s.g.row_lo) * pitch;
+    const double* f0 = s.b[B_F] + (size_t)(0 - s.g.row_lo) * pitch;
+    const int rrows = std::min(s.g.j1, P.ny) - std::max(s.g.j0, 1) + 1;
+    const dim3 rgrid((P.nx + 63) / 64, std::max(1, (rrows + 3) / 4));
+    HIPC(hipEventRecord(ev_a, st));
+    double res = tol + 1.0;  // channel-01.cpp:650
+    int cycles = 0;
+    long long launches = 0;
+    double fine = 0.0;
+    mg_cur[0] = p0;
+    while (res > tol && cycles < mg_max_cycles) {
+      launches += mgo_vcycle(p0, f0);
+      double* buf = mg_cur[0] == p0 ? X : mg_q0;
+      res_refresh(s.g, buf, st);  // channel-01.cpp:531-541: west and east columns, then south and north rows
+      check_launch("mgo_refresh");
+      HIPC(hipMemsetAsync(resmax, 0, RES_SHARDS * SHARD_STRIDE * sizeof(double), st));
+      open_resmax_kernel<CHANNEL><<<rgrid, 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax);
+      check_launch("resmax");
+      HIPC(hipMemcpyAsync(h_shard, resmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPC(hipStreamSynchronize(st));
+      res = 0.0;
+      for (int q = 0; q < RES_SHARDS; ++q) res = std::max(res, h_shard[q * SHARD_STRIDE]);
+      launches += 2;
+      ++cycles;
+      float a = 0.f, b = 0.f;
+      HIPC(hipEventElapsedTime(&a, mg_ev[0], mg_ev[1]));
+      HIPC(hipEventElapsedTime(&b, mg_ev[2], mg_ev[3]));
+      fine += (double)a + (double)b;
+    }
+    if (mg_cur[0] != p0) {
+      // an odd number of fused launches: the field is in the second buffer. Rows 1 .. ny whole (their
+      // ghost columns are refreshed), the ghost rows over columns 1 .. nx: the corners stay p's own.
+      const double* q = mg_cur[0];
+      HIPC(hipMemcpyAsync(p0 + pitch, q + pitch, (size_t)P.ny * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
+      HIPC(hipMemcpyAsync(p0 + 1, q + 1, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      const size_t top = (size_t)(P.ny + 1) * pitch + 1;
+      HIPC(hipMemcpyAsync(p0 + top, q + top, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      mg_cur[0] = p0;
+    }
+    HIPC(hipEventRecord(ev_b, st));
+    HIPC(hipEventSynchronize(ev_b));
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
+    const long long sweeps = (long long)cycles * (mg_nu1 + mg_nu2);
+    T.poisson_ms += ms;
+    T.poisson_launches += launches;
+    T.poisson_sweeps += sweeps;  // (level-0 sweeps)
+    T.poisson_cell_updates += (long long)P.nx * P.ny * sweeps;
+    mgi.solves += 1;
+    mgi.cycles += cycles;
+    mgi.launches += launches;
+    mgi.solve_ms += ms;
+    mgi.fine_ms += fine;
+    if (out) {
+      out->sor_iterations = cycles;
+      out->residual = res;
+    }
+  }
+
   void solve(cfd_step_info* out) {
+    if (mgo_on) {
+      T.sor_kernel = CFD_SOR_MULTIGRID;
+      solve_mg_open(out);
+      return;
+    }
     if (mg_on) {
       T.sor_kernel = CFD_SOR_MULTIGRID;
       solve_mg(out);

@@ -178,7 +178,11 @@ enum cfd_sor_kernel {
  * without a valid plan such as the reference's 63^2 (grid rule), more than one strip (strip rule)
  * and rank solvers (rank rule).
  */
-enum cfd_poisson_method { CFD_POISSON_SOR = 0, CFD_POISSON_MULTIGRID = 1 };
+enum cfd_poisson_method {
+  CFD_POISSON_SOR = 0,
+  CFD_POISSON_MULTIGRID = 1,      /* the cavity and Rayleigh-Benard */
+  CFD_POISSON_MULTIGRID_OPEN = 2  /* the channel (below; added within ABI 14) */
+};
 typedef struct cfd_mg_options {
   int pre_sweeps, post_sweeps, max_cycles;  /* 0 (or a NULL options pointer): 2, 2, 50 */
 } cfd_mg_options;
@@ -193,6 +197,28 @@ typedef struct cfd_mg_info {
 int cfd_get_mg_info(cfd_solver* s, cfd_mg_info* out);
 /* The plan of a parameter block (host only, no device needed); any output pointer may be NULL. */
 int cfd_mg_plan(const cfd_params* p, int* levels, int* coarse_nx, int* coarse_ny);
+/*
+ * CFD_POISSON_MULTIGRID_OPEN: the channel's multigrid solve (DESIGN.md §8 "The channel"), a second
+ * method beside the first - same options, same cfd_get_mg_info, cfd_timing.sor_kernel reports
+ * CFD_SOR_MULTIGRID, CFD_POISSON_SOR switches back. New symbols and one enum value within ABI 14.
+ *
+ * The channel's operator (channel-01.cpp:642-688) has dx != dy, Neumann west / south / north and a
+ * Dirichlet zero in the east ghost column; its solve starts from the pressure the solver holds (no
+ * zeroing) and stops at tol = max(tol_factor * (max|source| or 1), abs_tol), tested on the
+ * reference's own residual over ghosts refreshed as the reference refreshes them; at least one
+ * cycle runs. Levels are semi-coarsened: with r = (hy / hx)^2 of a level, r > 2 halves x only,
+ * r < 1/2 halves y only, otherwise both; a direction can be halved while its size is even and >= 8,
+ * and a level whose chosen direction(s) cannot be halved is the coarsest. Coarse levels keep the
+ * east zero where the finest grid has it. Valid with 2 .. 16 levels and a coarsest level of at most
+ * 4096 cells. Refusals (CFD_E_ARG, cfd_last_error naming the rule): the cavity, Rayleigh-Benard
+ * (they have CFD_POISSON_MULTIGRID) and the step (case rule), a grid without a valid plan such as
+ * the reference's 93 x 31 (grid rule), more than one strip (strip rule), rank solvers (rank rule),
+ * bad options.
+ *
+ * cfd_mg_open_plan (host only): the number of levels and every level's size in arrays of 16
+ * entries (unused entries 0); any pointer may be NULL.
+ */
+int cfd_mg_open_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny);
 
 /* Library / ABI info. */
 int cfd_abi_version(void);
