@@ -2851,7 +2851,9 @@ cfd_solver* cfd_create(const cfd_params* p, int device, int n_strips) {
   guard([&] {
     if (!p) throw Error(CFD_E_ARG, "null params");
     if (n_strips < 1) throw Error(CFD_E_ARG, "n_strips must be >= 1");
-    if (p->ny < n_strips * cfd::HALO) throw Error(CFD_E_ARG, "each strip needs at least 8 rows (the SOR halo depth)");
+    // (strips send HALO owned rows to each neighbour; one domain exchanges nothing: any ny >= 2, validate)
+    if (n_strips > 1 && p->ny < n_strips * cfd::HALO)
+      throw Error(CFD_E_ARG, "each strip needs at least 8 rows (the SOR halo depth)");
     std::vector<std::pair<int, int>> rows;
     for (int k = 0; k < n_strips; ++k) {
       const int a = 1 + (int)((long long)p->ny * k / n_strips);

@@ -238,7 +238,8 @@ int cfd_params_init_rb(double ra, double pr, int nx, int ny, double dt, cfd_para
  * (cavity-01.cpp:355, channel-01.cpp:336, backwards_step-01.cpp:377) —
  * allocateFields + setupGeometry + the initial applyBoundaryConditions of the
  * open cases. The grid is split into `n_strips` row strips on this device
- * (1 = one domain); strips exchange halo rows after every stage. */
+ * (1 = one domain, any ny >= 2); strips exchange halo rows after every stage
+ * and need ny >= 8 * n_strips. */
 cfd_solver* cfd_create(const cfd_params* p, int device, int n_strips);
 
 /* Multi-process construction: this rank owns interior rows

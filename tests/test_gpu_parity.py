@@ -74,13 +74,16 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
-@pytest.mark.parametrize("strips", [1, 3])
-@pytest.mark.parametrize("case", CASES)
-def test_stencil_phases_bitexact(case, strips):
-    cp = small_params(case)
-    g = C.solver_for(cp, ordering="rb", n_strips=strips)
+def stencil_phases(cp, ordering, strips, tuning=None, seed=1234):
+    """Every stencil phase once on random fields, GPU against the oracle, bit for bit.
+    The two sums the red-black order re-associates (the open cases' source mean,
+    the kinetic energy: tree sums there, the reference's sequential loop in the
+    reference order) are exact in the reference order and within 1e-12 in red-black."""
+    case = C.CASE_NAMES[cp.case_id]
+    closed = case in ("cavity", "rayleigh_benard")
+    g = C.solver_for(cp, ordering=ordering, n_strips=strips, tuning=tuning)
     o = O.Oracle(cp)
-    rng = np.random.default_rng(1234)
+    rng = np.random.default_rng(seed)
     nx, ny = cp.nx, cp.ny
     set_both(g, o, "u", rng.standard_normal((ny + 2, nx + 1)), cp)
     set_both(g, o, "v", rng.standard_normal((ny + 1, nx + 2)), cp)
@@ -95,7 +98,15 @@ def test_stencil_phases_bitexact(case, strips):
     assert_bits(g.field("us"), ofield(o, "us", cp), "tentative u*")
     assert_bits(g.field("vs"), ofield(o, "vs", cp), "tentative v*")
 
-    if case != "cavity":
+    if case == "rayleigh_benard":  # bc_temperature_kernel + thermal_kernel (buoyancy into v*, T advanced)
+        set_both(g, o, "t", rng.standard_normal((ny + 2, nx + 2)), cp)
+        g.advanceTemperature()
+        o.temperature_bc()
+        o.thermal()
+        assert_bits(g.field("vs"), ofield(o, "vs", cp), "v* with buoyancy")
+        assert_bits(g.field("t")[1:-1, 1:-1], o.field("t")[1:-1, 1:-1], "T after one update")
+
+    if not closed:
         g.applyTentativeBoundaryConditions()
         o.velocity_bc(True)
         assert_bits(g.field("us"), ofield(o, "us", cp), "BC u*")
@@ -103,8 +114,10 @@ def test_stencil_phases_bitexact(case, strips):
 
     g.buildSourceTerm()
     o.source()
-    if case == "cavity":
-        assert_bits(g.field("src"), o.field("src"), "source")
+    if closed or ordering == "lex":
+        assert_bits(g.field("src")[1:-1, 1:-1], o.field("src")[1:-1, 1:-1], "source")
+        if case != "rayleigh_benard":
+            assert_bits(g.field("src"), o.field("src"), "source")
     else:  # mean removal: tree sum vs sequential sum
         np.testing.assert_allclose(g.field("src"), o.field("src"), rtol=0, atol=1e-12 * np.abs(o.field("src")).max())
 
@@ -120,9 +133,104 @@ def test_stencil_phases_bitexact(case, strips):
     md, ke = g.statistics()
     omd, oke = o.stats()
     assert md == omd
-    assert ke == pytest.approx(oke, rel=1e-12)
+    if ordering == "lex":
+        assert ke == oke
+    else:
+        assert ke == pytest.approx(oke, rel=1e-12)
     assert_bits(g.field("uc"), o.field("uc"), "u_center")
     assert_bits(g.field("vc"), o.field("vc"), "v_center")
+    g.close()
+
+
+@pytest.mark.parametrize("strips", [1, 3])
+@pytest.mark.parametrize("case", CASES)
+def test_stencil_phases_bitexact(case, strips):
+    stencil_phases(small_params(case), "rb", strips)
+
+
+# Shapes at the launch-geometry edges of the stencil kernels (solver.hip):
+#  * the predictor's column tiles of 112 (ct = nx/112 + 1): nx = 111, 112, 113, 223, 224, 225;
+#  * its row bands (tent_th rows; the knob set to 5 keeps the grids small): ny = 9, 10, 11;
+#  * the 64-column x 4-row blocks of grid2d and the cavity's 128-column pair_grid passes:
+#    nx = 62, 63, 64, 127, 128, 129, and 3, 4, 5 rows;
+#  * the row pitch (nx + 3 rounded up to 16): nx = 13 (pitch nx + 3 exactly), 14, 29;
+#  * two and three strips of 8 rows, and 8 + 9;
+#  * the tiny grids of test_gpu_shapes.py.
+# (nx, ny, tent_th or 0)
+EDGE_SHAPES = [(111, 9, 0), (112, 9, 0), (113, 9, 0), (223, 9, 0), (224, 9, 0), (225, 9, 0),
+               (13, 9, 5), (14, 10, 5), (29, 11, 5), (113, 11, 5),
+               (62, 3, 0), (63, 4, 0), (64, 5, 0), (127, 5, 0), (128, 3, 0), (129, 4, 0),
+               (64, 16, 0), (129, 17, 5), (113, 24, 5)]
+TINY_SHAPES = {"cavity": [(2, 2), (2, 5), (5, 2), (3, 3), (7, 4), (13, 9)],
+               "channel": [(2, 2), (3, 2), (2, 7), (6, 3), (13, 5)],
+               "backwards_step": [(4, 2), (4, 4), (8, 4), (5, 3), (9, 2), (16, 4)],
+               "rayleigh_benard": [(2, 2), (4, 2), (5, 3)]}
+# the step's block column on the predictor's tile edge (step_i = nx/4 = 111, 112, 113)
+STEP_EDGE = [(444, 8, 0), (448, 8, 0), (452, 8, 0), (444, 16, 5)]
+
+
+def edge_cases():
+    out = []
+    for case in CASES + ["rayleigh_benard"]:
+        shapes = EDGE_SHAPES + [(nx, ny, 0) for nx, ny in TINY_SHAPES[case]]
+        if case == "backwards_step":
+            shapes = shapes + STEP_EDGE
+        out += [(case, nx, ny, th) for nx, ny, th in shapes]
+    return out
+
+
+def edge_params(case, nx, ny):
+    if case == "rayleigh_benard":
+        return C.make_params(case, nx=nx, ny=ny, ra=2e4)
+    return C.make_params(case, nx=nx, ny=ny)
+
+
+@pytest.mark.parametrize("ordering", ["rb", "lex"])
+@pytest.mark.parametrize("case,nx,ny,tent_th", edge_cases(), ids=lambda v: str(v))
+def test_stencil_phases_at_launch_edges(case, nx, ny, tent_th, ordering):
+    """test_stencil_phases_bitexact's body at the shapes above, in both orders,
+    on one strip and on the most strips the rows allow (8 each), up to 3."""
+    cp = edge_params(case, nx, ny)
+    tuning = {"tent_th": tent_th} if tent_th else None
+    for strips in sorted({1, max(1, min(3, ny // 8))}):
+        stencil_phases(cp, ordering, strips, tuning, seed=1000 * nx + ny)
+
+
+@pytest.mark.parametrize("ordering", ["rb", "lex"])
+@pytest.mark.parametrize("step_x,h_inlet", [(0.2, 1.0), (2.0, 1.9)])
+def test_stencil_phases_degenerate_blocks(step_x, h_inlet, ordering):
+    """The step's block one cell wide (64x32, step_i = 1) and one cell high
+    (40x10, inlet_jmax = ny-1 = 9), as the reference variants have them."""
+    nx, ny = (64, 32) if step_x == 0.2 else (40, 10)
+    cp = C.make_params("backwards_step", nx=nx, ny=ny)
+    cp.step_x, cp.h_inlet = step_x, h_inlet
+    assert (cp.step_i == 1) != (cp.inlet_jmax == ny - 1)
+    stencil_phases(cp, ordering, 1)
+    if ordering == "rb":  # (the reference order keeps such a block on one strip)
+        stencil_phases(cp, ordering, min(3, ny // 8))
+
+
+@pytest.mark.parametrize("ordering", ["rb", "lex"])
+@pytest.mark.parametrize("case,nx,ny", [("cavity", 2, 2), ("cavity", 129, 5), ("channel", 2, 7), ("channel", 113, 9),
+                                        ("backwards_step", 4, 2), ("backwards_step", 448, 8)])
+def test_source_maximum_sets_the_tolerance(case, nx, ny, ordering):
+    """srcmax_kernel on its own: a source set from the host, then one capped
+    solve. The tolerance comes from max|f| over the interior, so the iteration
+    count and the residual equal the oracle's with the same source."""
+    cp = C.make_params(case, nx=nx, ny=ny, max_iters=200)
+    cp.tol_factor = 1e-3
+    g = C.solver_for(cp, ordering=ordering)
+    o = O.Oracle(cp, ordering=O.LEX if ordering == "lex" else O.RB)
+    rng = np.random.default_rng(nx * 100 + ny)
+    f = np.zeros((ny + 2, nx + 2))
+    f[1:ny + 1, 1:nx + 1] = rng.standard_normal((ny, nx)) * (0.05 if case == "cavity" else 10.0)
+    f[o.mask() == 0] = 0.0
+    # the largest value in the last interior cell: a maximum that skips it changes the stop
+    f[ny, nx] = 3.0 * np.abs(f).max()
+    set_both(g, o, "src", f, cp)
+    assert g.solverPressurePoisson() == o.poisson()
+    assert_bits(g.field("p"), o.field("p"), "pressure")
+    g.close()
 
 
 @pytest.mark.parametrize("strips", [1, 2])

@@ -1,0 +1,364 @@
+"""The GPU engines off the reference's default grids: tiny grids (2 to 16
+cells in a direction), the reference-variant grids of
+tests/golden/ref_variants.json (test_oracle_variants.py pins the oracle to
+them), degenerate step blocks and minimal strips.
+
+Every comparison is bit for bit: iteration counts, residuals, fields,
+statistics, log lines and frame hashes. There is no tolerance in this file.
+Two sums are re-associated by design in the red-black order only (a tree sum
+on the GPU, a sequential one in the reference): the open cases' source mean
+and the kinetic energy. They are held to 1e-12 in
+test_gpu_parity.py::test_stencil_phases_at_launch_edges and left out here: a
+red-black step of an open case runs by phases with the oracle solving the
+GPU's own source (everything else of the step - predictor, boundary rules,
+tolerance, solve, correction - is then compared exactly), and the red-black
+statistics compare the maximum divergence only.
+
+Each test asserts through timing().sor_kernel which engine ran the solve, so a
+shape an engine declines fails here instead of passing on another engine.
+
+Engines (include/cfd_amd.h enum cfd_sor_kernel):
+  reference order  smlex  one workgroup, p in LDS (default where the grid fits)
+                   lexw   the multi-block march (small_solve off, resident off)
+                   lex    poisson_lex_kernel: a step whose block is under 2 cells
+                          wide or high (step_i = 1 or inlet_jmax = ny-1)
+  red-black        small  one workgroup (default), march, tile, resident
+"""
+from __future__ import annotations
+
+import hashlib
+import io
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+import cfd_amd as C  # noqa: E402
+from cfd_amd import _lib  # noqa: E402
+import oracle as O  # noqa: E402
+from test_gpu_parity import assert_bits, ofield  # noqa: E402
+from test_oracle_variants import VARIANTS, params_of  # noqa: E402
+
+CAVITY, CHANNEL, BACKSTEP, RBC = C.CAVITY, C.CHANNEL, C.BACKSTEP, C.RAYLEIGH_BENARD
+BIN = os.path.join(ROOT, "computational-fluid-dynamics_amd", "bin")
+ANSI = re.compile(r"\x1b\[[0-9;]*m")
+VTK_BASE = {"cavity": "cavity_flow", "channel": "channel_flow", "backwards_step": "backwards_step"}
+
+# engine -> (ordering, solver keywords)
+ENGINES = {
+    "smlex": ("lex", {}),
+    "lexw": ("lex", {"small_solve": "off", "tuning": {"resident": 0}}),
+    "small": ("rb", {}),
+    "march": ("rb", {"small_solve": "off", "tuning": {"tile_rounds": 0, "resident": 0}}),
+    "tile": ("rb", {"small_solve": "off", "tuning": {"tile_rounds": 1, "resident": 0}}),
+    "resident": ("rb", {"small_solve": "off", "tuning": {"tile_rounds": 1, "resident": 1}}),
+    "resident-lex": ("lex", {"small_solve": "off", "tuning": {"resident": 1}}),
+}
+
+
+def degenerate(cp) -> bool:
+    """A step whose block is under 2 cells wide or high (solver.hip step_lexw_ok)."""
+    return cp.case_id == BACKSTEP and not (cp.step_i >= 2 and 1 <= cp.inlet_jmax <= cp.ny - 2)
+
+
+def engine_that_runs(cp, engine: str) -> str:
+    """The engine the solve of `cp` must report when `engine` is asked for."""
+    if engine in ("smlex", "lexw", "resident-lex") and degenerate(cp):
+        return "lex"  # neither one-workgroup nor multi-block march: poisson_lex_kernel
+    if engine in ("resident", "resident-lex"):
+        return "resident"
+    return engine
+
+
+def kernel_of(g) -> str:
+    return _lib.SOR_KERNEL[g.timing().sor_kernel]
+
+
+def tiny(case: str, nx: int, ny: int, **kw):
+    if case == "rayleigh_benard":
+        kw.setdefault("ra", 2e4)
+    return C.make_params(case, nx=nx, ny=ny, **kw)
+
+
+def start_pair(cp, engine, n_strips=1):
+    ordering, kw = ENGINES[engine]
+    g = C.solver_for(cp, ordering=ordering, n_strips=n_strips, **kw)
+    o = O.Oracle(cp, ordering=O.LEX if ordering == "lex" else O.RB)
+    if cp.case_id in (CAVITY, RBC):
+        g.applyBoundaryConditions()  # cavity-01.cpp:380 (the open cases: in the constructor)
+    o.velocity_bc(False)
+    return g, o, ordering
+
+
+def step_pair(g, o, cp, ordering):
+    """One time step on both. Red-black open cases: by phases, the oracle solving
+    the GPU's source (its mean is a tree sum there; module docstring)."""
+    if ordering == "lex" or cp.case_id in (CAVITY, RBC):
+        return g.step(), o.step()
+    g.computeTentativeVelocities()
+    o.tentative()
+    g.applyTentativeBoundaryConditions()
+    o.velocity_bc(True)
+    g.buildSourceTerm()
+    o.source()
+    o.field("src")[...] = g.field("src")
+    a, b = g.solverPressurePoisson(), o.poisson()
+    g.applyPressureCorrection()
+    o.correct()
+    g.applyBoundaryConditions()
+    o.velocity_bc(False)
+    return a, b
+
+
+def compare_state(g, o, cp, ordering, what):
+    for n in ("u", "v", "p"):
+        assert_bits(g.field(n), ofield(o, n, cp), f"{what} {n}")
+    if cp.case_id == RBC:
+        assert_bits(g.field("t")[1:-1, 1:-1], o.field("t")[1:-1, 1:-1], f"{what} T")
+    md, ke = g.statistics()
+    omd, oke = o.stats()
+    assert md == omd, what
+    if ordering == "lex":
+        assert ke == oke, what
+    assert_bits(g.field("uc"), o.field("uc"), f"{what} u_center")
+    assert_bits(g.field("vc"), o.field("vc"), f"{what} v_center")
+
+
+def run_steps(cp, engine, steps=3, n_strips=1, runs=None):
+    g, o, ordering = start_pair(cp, engine, n_strips)
+    runs = engine_that_runs(cp, engine) if runs is None else runs
+    what = f"{C.CASE_NAMES[cp.case_id]} {cp.nx}x{cp.ny} {engine}"
+    its = []
+    for k in range(steps):
+        a, b = step_pair(g, o, cp, ordering)
+        assert a == b, (what, k, a, b)
+        assert kernel_of(g) == runs, (what, kernel_of(g))
+        its.append(a[0])
+    compare_state(g, o, cp, ordering, what)
+    g.close()
+    return its
+
+
+# ---------------------------------------------------------------- B.1 ----
+# the product against the reference variants
+
+def variant_lines(name, g, tmp_path):
+    cp = g.params
+    out, err = io.StringIO(), io.StringIO()
+    g.run(output_directory=str(tmp_path), out=out, err=err)
+    assert [l for l in out.getvalue().splitlines() if l.startswith("Step ")] == VARIANTS[name]["steps"]
+    assert err.getvalue().splitlines() == VARIANTS[name]["warnings"]
+    base = VTK_BASE[VARIANTS[name]["case"]]
+    for fr, digest in VARIANTS[name]["vtk_sha256"].items():
+        data = (tmp_path / f"{base}_{int(fr):06d}.vtk").read_bytes()
+        assert hashlib.sha256(data).hexdigest() == digest, (name, fr)
+    assert cp.total_steps == VARIANTS[name]["last_frame"]
+
+
+@pytest.mark.parametrize("name", sorted(VARIANTS))
+def test_python_run_reproduces_reference_variant(name, tmp_path):
+    """run() in the reference order prints the variant binary's Step lines and
+    capped-solve warnings character for character and writes its first and last
+    frame byte for byte (default engine: smlex, or lex for a degenerate block)."""
+    cp = params_of(name)
+    g = C.solver_for(cp, ordering="lex")
+    variant_lines(name, g, tmp_path)
+    assert kernel_of(g) == engine_that_runs(cp, "smlex")
+
+
+CLI_VARIANTS = sorted(n for n, v in VARIANTS.items() if not {"STEP_LOCATION", "HEIGHT_INLET"} & set(v["constants"]))
+
+
+@pytest.mark.parametrize("name", CLI_VARIANTS)
+def test_binary_reproduces_reference_variant(name, tmp_path):
+    """The drop-in binary with --Nx/--Ny/--final-time/--print-interval (and --Re):
+    the variant's header values (params.cpp's derivation), Step lines, warnings
+    and frame files. (The two block-geometry variants have no flag.)"""
+    v = VARIANTS[name]
+    cp = params_of(name)
+    args = ["--Nx", str(cp.nx), "--Ny", str(cp.ny), "--final-time", v["constants"]["final_time"],
+            "--print-interval", str(cp.print_interval), "--save-interval", str(cp.save_interval)]
+    if {"reynolds_number", "REYNOLDS_NUMBER"} & set(v["constants"]):
+        args += ["--Re", repr(cp.re)]
+    r = subprocess.run([os.path.join(BIN, v["case"]), *args], cwd=tmp_path, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    out = [ANSI.sub("", l) for l in r.stdout.splitlines()]
+    err = [ANSI.sub("", l) for l in r.stderr.splitlines()]
+    assert [l for l in out if l.startswith("Step ")] == v["steps"]
+    assert [l for l in err if "Warning" in l] == v["warnings"]
+    for h in v["header"]:
+        assert h in out, h
+    for fr, digest in v["vtk_sha256"].items():
+        data = (tmp_path / "vtk_output" / f"{VTK_BASE[v['case']]}_{int(fr):06d}.vtk").read_bytes()
+        assert hashlib.sha256(data).hexdigest() == digest, (name, fr)
+
+
+# ---------------------------------------------------------------- B.2 ----
+# every engine that accepts the shape, against the oracle
+
+TINY = [("cavity", 2, 2), ("cavity", 2, 5), ("cavity", 5, 2), ("cavity", 3, 3), ("cavity", 7, 4), ("cavity", 13, 9),
+        ("channel", 2, 2), ("channel", 3, 2), ("channel", 2, 7), ("channel", 6, 3), ("channel", 13, 5),
+        ("backwards_step", 4, 2), ("backwards_step", 4, 4), ("backwards_step", 8, 4), ("backwards_step", 5, 3),
+        ("backwards_step", 9, 2), ("backwards_step", 16, 4),
+        ("rayleigh_benard", 2, 2), ("rayleigh_benard", 4, 2), ("rayleigh_benard", 5, 3)]
+STEP_ENGINES = ["smlex", "lexw", "small", "march", "tile"]
+CAP = 300  # sweeps per solve on the larger variant grids (their natural solves run thousands)
+
+
+@pytest.mark.parametrize("engine", STEP_ENGINES)
+@pytest.mark.parametrize("case,nx,ny", TINY, ids=[f"{c}-{x}x{y}" for c, x, y in TINY])
+def test_tiny_grid_steps(case, nx, ny, engine):
+    """Three whole steps of a grid under 16 cells wide and under 10 high on
+    each engine, natural stops (channel 2x7 runs ~3800 sweeps per solve)."""
+    run_steps(tiny(case, nx, ny), engine)
+
+
+@pytest.mark.parametrize("engine", STEP_ENGINES)
+@pytest.mark.parametrize("name", sorted(VARIANTS))
+def test_variant_grid_steps(name, engine):
+    """Three whole steps of every reference-variant shape on each engine (the
+    variants' own geometry: step_i = 1, 112, inlet_jmax = ny-1 included);
+    grids over 400 cells capped at CAP sweeps per solve."""
+    cp = params_of(name)
+    if cp.nx * cp.ny > 400:
+        cp.max_iters = CAP
+    run_steps(cp, engine)
+
+
+@pytest.mark.parametrize("case,nx,ny", [("cavity", 7, 4), ("cavity", 2, 2), ("channel", 6, 3)])
+@pytest.mark.parametrize("engine", ["resident", "resident-lex"])
+def test_tiny_grid_on_resident(case, nx, ny, engine):
+    """The register-resident launch takes a tiny cavity or channel as one tile
+    (resident.hip res_plan: one column tile, one row tile of its halo depth)."""
+    run_steps(tiny(case, nx, ny), engine)
+
+
+@pytest.mark.parametrize("engine", STEP_ENGINES)
+@pytest.mark.parametrize("case,nx,ny", [("cavity", 7, 4), ("channel", 6, 3), ("backwards_step", 8, 4),
+                                        ("backwards_step", 5, 3)])
+def test_cap_around_the_natural_stop(case, nx, ny, engine):
+    """max_iters one below and one above the first solve's natural stop: the
+    capped solve reports the cap and its residual, the other stops as before."""
+    ordering = ENGINES[engine][0]
+    o = O.Oracle(tiny(case, nx, ny), ordering=O.LEX if ordering == "lex" else O.RB)
+    o.velocity_bc(False)
+    natural = o.step()[0]
+    assert 3 < natural < 9000
+    below = run_steps(tiny(case, nx, ny, max_iters=natural - 1), engine, steps=2)
+    above = run_steps(tiny(case, nx, ny, max_iters=natural + 1), engine, steps=2)
+    if ordering == "lex" or case == "cavity":  # (a red-black open case solves the GPU's source)
+        assert below[0] == natural - 1 and above[0] == natural
+
+
+# ---------------------------------------------------------------- B.3 ----
+# poisson_lex_kernel
+
+LEX_GRIDS = ["step_64x32_i1", "step_40x10_j9", "step_4x2"]  # step_i = 1; inlet_jmax = ny-1; both
+
+
+def lex_params(name, **changes):
+    cp = params_of(name)
+    assert degenerate(cp)
+    for k, v in changes.items():
+        setattr(cp, k, v)
+    return cp
+
+
+@pytest.mark.parametrize("name", sorted(LEX_GRIDS))
+def test_lex_kernel_capped_and_converging(name):
+    """poisson_lex_kernel (kernels.hpp), the reference-order engine of a step
+    whose block is one cell wide (step_i = 1) or high (inlet_jmax = ny-1), with
+    small_solve off: a run capped at 250 sweeps and a converging one
+    (tol_factor 1e-2: the stop is found while later iterations already ran, so
+    the kernel restores the initial field and replays to the stop), each three
+    whole steps against the oracle.
+
+    Why its `for (;;)` ends at these shapes. One workgroup runs the loop; every
+    pass ends in two block-wide barriers that all 1024 threads reach (the cell
+    loop has no early exit, only `continue`), and tau grows by one per pass
+    unless a replay starts. Thread 0 tests iteration kc = (tau - nx - ny) / 3 - 1
+    when that is a whole number >= 1, so kc takes every value 1, 2, ... in turn.
+    At kc = max_iters at the latest (`kc >= max_iters`; a NaN residual stops
+    sooner, `!(rk > tol)`) it sets s_stop, or s_replay with s_kmax = kc. A replay
+    happens once (the `s_replay && !replay` branch needs the pass to have begun
+    with replay false), resets tau to 0 and sets s_stop at kc >= s_kmax. So the
+    loop makes at most 2 (nx + ny + 3 max_iters + 3) + 2 passes: 64x32 with
+    max_iters 10000 under 61000, each a pass over 2 cells per thread. Its
+    indices stay inside the stored rows 0 .. ny+1 and columns 0 .. nx+1 for
+    any nx, ny >= 1 (at() of j+-1, i+-1 of an interior cell), and the residual
+    window needs (nx + ny) / 3 + 8 < 4096, which validate() checks."""
+    its = run_steps(lex_params(name, max_iters=250), "lexw", runs="lex")
+    assert max(its) == 250 or name == "step_4x2"  # (4x2 converges in fewer sweeps; 5 caps it below)
+    if name == "step_4x2":
+        assert run_steps(lex_params(name, max_iters=5), "lexw", runs="lex") == [5, 5, 5]
+    cp = lex_params(name, tol_factor=1e-2, abs_tol=0.0)
+    its = run_steps(cp, "lexw", runs="lex")
+    assert all(1 < i < cp.max_iters for i in its), its
+
+
+@pytest.mark.parametrize("name", sorted(LEX_GRIDS))
+def test_lex_kernel_reproduces_reference_variant(name, tmp_path):
+    """The same engine against the reference variant's own log and frames."""
+    cp = lex_params(name)
+    g = C.solver_for(cp, ordering="lex", small_solve="off")
+    variant_lines(name, g, tmp_path)
+    assert kernel_of(g) == "lex"
+
+
+def test_lex_kernel_grids_default_to_it():
+    """With small_solve left on auto a degenerate block still runs
+    poisson_lex_kernel: the one-workgroup LDS solve declines it (smlex_fits)."""
+    for nx, ny in ((4, 2), (4, 4), (5, 3), (9, 2)):
+        cp = tiny("backwards_step", nx, ny)
+        assert degenerate(cp)
+        g = C.solver_for(cp, ordering="lex")
+        g.step()
+        assert kernel_of(g) == "lex"
+        g.close()
+
+
+# ---------------------------------------------------------------- B.4 ----
+# minimal strips: cfd_create accepts ny >= 8 n_strips
+
+@pytest.mark.parametrize("ordering", ["lex", "rb"])
+@pytest.mark.parametrize("ny,n_strips", [(16, 2), (17, 2), (24, 3)])
+@pytest.mark.parametrize("case", ["cavity", "channel", "backwards_step"])
+def test_minimal_strips(case, ny, n_strips, ordering):
+    """Strips of 8 rows (16 / 2, 24 / 3) and of 8 + 9 rows (17 / 2): three whole
+    steps against the oracle in both orders. Strips run the multi-block
+    engines only (lexw; red-black: march). At 20 columns the step's block is
+    5 x ny/2 cells, so validate() refuses none of these."""
+    cp = C.make_params(case, nx=20, ny=ny, max_iters=400)
+    assert not degenerate(cp)
+    g = C.solver_for(cp, ordering=ordering, n_strips=n_strips)
+    o = O.Oracle(cp, ordering=O.LEX if ordering == "lex" else O.RB)
+    if case == "cavity":
+        g.applyBoundaryConditions()
+    o.velocity_bc(False)
+    for k in range(3):
+        a, b = step_pair(g, o, cp, ordering)
+        assert a == b, (k, a, b)
+        assert kernel_of(g) == ("lexw" if ordering == "lex" else "march")
+    compare_state(g, o, cp, ordering, f"{case} 20x{ny} / {n_strips} strips {ordering}")
+    g.close()
+
+
+def test_strip_rule_is_for_strips_only():
+    """cfd_create's "each strip needs at least 8 rows" holds for n_strips > 1
+    (strips send 8 owned rows to each neighbour). One domain exchanges nothing
+    and takes any ny >= 2: before this file it refused ny < 8 as well, so no
+    grid of the reference variants under 8 rows could run."""
+    for ny, n_strips in ((15, 2), (23, 3), (7, 2)):
+        with pytest.raises(_lib.CfdError, match="at least 8 rows"):
+            C.solver_for(C.make_params("channel", nx=12, ny=ny), n_strips=n_strips)
+    with pytest.raises(_lib.CfdError, match="at least 2 interior cells"):
+        C.solver_for(C.CaseParams(**{**vars(C.make_params("channel", nx=12, ny=2)), "ny": 1}))
+    g = C.solver_for(C.make_params("channel", nx=12, ny=2))
+    g.step()
+    assert kernel_of(g) == "smlex"
+    g.close()
