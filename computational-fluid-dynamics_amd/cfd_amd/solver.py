@@ -55,7 +55,8 @@ class _SolverBase:
         poisson: "sor" (the reference's solve, the default) or "multigrid" (V-cycles to
         the reference's tolerance: the cavity and Rayleigh-Benard on one strip, no ranks;
         see set_poisson_method) or "multigrid-open" (the channel's multigrid solve, one
-        strip, no ranks). mg_options: pre_sweeps / post_sweeps / max_cycles."""
+        strip, no ranks) or "multigrid-step" (the backwards-facing step's, likewise).
+        mg_options: pre_sweeps / post_sweeps / max_cycles."""
         self.params = params if params is not None else make_params(self.CASE)
         if self.params.case_id != self.CASE:
             raise ValueError(f"{type(self).__name__} needs case {CASE_NAMES[self.CASE]}")
@@ -92,7 +93,11 @@ class _SolverBase:
         residual). "sor" switches back. Raises CfdError naming the rule for the channel,
         the step, strips, ranks and grids without a plan (mg_plan). "multigrid-open" is
         the channel's method (semi-coarsened levels, a warm start from the current p; the
-        cavity, Rayleigh-Benard and the step are refused; plans: mg_open_plan)."""
+        cavity, Rayleigh-Benard and the step are refused; plans: mg_open_plan).
+        "multigrid-step" is the backwards-facing step's (the channel's scheme over the fluid
+        cells, the block's corner coupling part of the operator; every other case and a
+        block under 2 cells wide or high, or an inlet under 2 cells high, are refused;
+        plans: mg_step_plan)."""
         if method not in _lib.POISSON:
             raise ValueError(f"poisson must be one of {sorted(_lib.POISSON)}, got {method!r}")
         opt = mg_options or {}
@@ -230,7 +235,7 @@ class _SolverBase:
         for k in range(1, total + 1):
             t = k * p.dt
             it, res = self.step()
-            cap = self._mg_max_cycles if self.poisson in ("multigrid", "multigrid-open") else p.max_iters  # (cycles in the iteration column)
+            cap = self._mg_max_cycles if self.poisson in ("multigrid", "multigrid-open", "multigrid-step") else p.max_iters  # (cycles in the iteration column)
             if it >= cap:
                 print(warning_line(p.case_id, cap, res), file=err)
             if k % p.print_interval == 0 or k == total:
@@ -324,6 +329,15 @@ def mg_open_plan(params: CaseParams) -> list[tuple[int, int]]:
     cp = to_cparams(params)
     lv, ax, ay = ctypes.c_int(), (ctypes.c_int * 16)(), (ctypes.c_int * 16)()
     _lib.check(_lib.lib().cfd_mg_open_plan(ctypes.byref(cp), ctypes.byref(lv), ax, ay), "cfd_mg_open_plan")
+    return [(ax[l], ay[l]) for l in range(lv.value)]
+
+
+def mg_step_plan(params: CaseParams) -> list[tuple[int, int]]:
+    """cfd_mg_step_plan (host only): [(nx, ny)] of every level of the backwards-facing step's
+    multigrid plan of these parameters; raises CfdError naming the rule where there is none."""
+    cp = to_cparams(params)
+    lv, ax, ay = ctypes.c_int(), (ctypes.c_int * 16)(), (ctypes.c_int * 16)()
+    _lib.check(_lib.lib().cfd_mg_step_plan(ctypes.byref(cp), ctypes.byref(lv), ax, ay), "cfd_mg_step_plan")
     return [(ax[l], ay[l]) for l in range(lv.value)]
 
 

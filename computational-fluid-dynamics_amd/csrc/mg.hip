@@ -22,8 +22,13 @@
 //
 // The second half of the file (mgo_*) is the channel's scheme: the same
 // launches with an anisotropic, semi-coarsened operator and a Dirichlet zero
-// in the east ghost column (tests/mg_open_reference.py).
+// in the east ghost column (tests/mg_open_reference.py). The third part
+// (mgs_*) is the backwards-facing step's: the channel's operator over the
+// fluid cells only, the block's corner coupling eliminated into its two fluid
+// neighbours (tests/mg_step_reference.py).
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "mg.hpp"
 
@@ -645,7 +650,404 @@ __global__ __launch_bounds__(MG_TAIL_THREADS) void mgo_tail_kernel(const MgoLeve
   }
 }
 
+// =============================================================== the step ==
+// The third scheme (mg.hpp "the step", tests/mg_step_reference.py): the
+// channel's streams, tile, halo and tail schemes over the fluid cells of the
+// backwards-facing step. Two integer compares tell fluid from solid; a
+// neighbour exists if it is inside the grid and fluid. The pair A = (jm+1,
+// si+1), B = (jm, si) is coupled through the eliminated corner solid and has
+// one colour: wherever a colour is updated, the thread that owns A forms both
+// new values from the values of before the phase and writes both, and the
+// thread that owns B writes nothing - no thread reads a cell another one
+// writes in the same phase.
+
+__device__ __forceinline__ bool mgs_fluid(const MgsLevel* L, int j, int i) { return i > L->si || j <= L->jm; }
+__device__ __forceinline__ bool mgs_is_a(const MgsLevel* L, int j, int i) { return j == L->jm + 1 && i == L->si + 1; }
+__device__ __forceinline__ bool mgs_is_b(const MgsLevel* L, int j, int i) { return j == L->jm && i == L->si; }
+
+// of a fluid cell (east and south of a fluid cell are fluid)
+__device__ __forceinline__ int mgs_mask(const MgsLevel* L, int j, int i) {
+  const int w = i > 1 && (i - 1 > L->si || j <= L->jm);
+  const int n = j < L->ny && (i > L->si || j + 1 <= L->jm);
+  return w | (int)(i < L->nx) << 1 | (int)(j > 1) << 2 | n << 3;
+}
+
+// The update of fluid cell (j, i), p pointing at it in a field with rows of P doubles (global memory or
+// LDS): Gauss-Seidel rdiag (sum - f), or the coarsest level's SOR p (1 - w) + (w rdiag) (sum - f);
+// sum = (cx pE + cx pW) + (cy pN + cy pS) over the neighbours that exist, with A's west term
+// (cx/2) p_B and B's north term (cy/2) p_A.
+__device__ __forceinline__ double mgs_update(const MgsLevel* L, const double* p, int P, int j, int i, double f, bool sor) {
+  const int k = mgs_mask(L, j, i);
+  const bool isa = mgs_is_a(L, j, i), isb = mgs_is_b(L, j, i);
+  const double tE = (k & 2) ? L->cx * p[1] : 0.0;
+  double tW = (k & 1) ? L->cx * p[-1] : 0.0;
+  double tN = (k & 8) ? L->cy * p[P] : 0.0;
+  const double tS = (k & 4) ? L->cy * p[-P] : 0.0;
+  if (isa) tW = L->chx * p[-P - 1];
+  if (isb) tN = L->chy * p[P + 1];
+  const double s = ((tE + tW) + (tN + tS)) - f;
+  if (sor) return p[0] * L->one_m_omega + (isa ? L->omrA : isb ? L->omrB : L->omr[k]) * s;
+  return (isa ? L->rdA : isb ? L->rdB : L->rdiag[k]) * s;
+}
+
+// residual of fine cell (j, i): the channel's, 0 in a solid cell; A's west term (cx/2)(p_B - c), B's north (cy/2)(p_A - c)
+__device__ __forceinline__ double mgs_resid_at(const MgsLevel* L, const double* p, const double* f, size_t P, int j,
+                                               int i) {
+  if (!mgs_fluid(L, j, i)) return 0.0;
+  const size_t o = (size_t)j * P + i;
+  const int k = mgs_mask(L, j, i);
+  const double c = p[o];
+  const double tE = (k & 2) ? L->cx * (p[o + 1] - c) : L->cE * (0.0 - c);
+  double tW = (k & 1) ? L->cx * (p[o - 1] - c) : 0.0;
+  double tN = (k & 8) ? L->cy * (p[o + P] - c) : 0.0;
+  const double tS = (k & 4) ? L->cy * (p[o - P] - c) : 0.0;
+  if (mgs_is_a(L, j, i)) tW = L->chx * (p[o - P - 1] - c);
+  if (mgs_is_b(L, j, i)) tN = L->chy * (p[o + P + 1] - c);
+  return ((tE + tW) + (tN + tS)) - f[o];
+}
+
+// Coarse source of cell (J, I) of level Lf + 1 (mgo_restrict_cell's three kinds); 0 in a solid coarse cell,
+// whose children are all solid (a halved direction's block edge is even).
+__device__ __forceinline__ double mgs_restrict_cell(const MgsLevel* Lf, const double* p, const double* f, size_t P, int J,
+                                                    int I) {
+  if (!mgs_fluid(Lf + 1, J, I)) return 0.0;
+  if (Lf->kind == MGO_X) {
+    const double rW = mgs_resid_at(Lf, p, f, P, J, 2 * I - 1), rE = mgs_resid_at(Lf, p, f, P, J, 2 * I);
+    return -0.5 * (rW + rE);
+  }
+  if (Lf->kind == MGO_Y) {
+    const double rS = mgs_resid_at(Lf, p, f, P, 2 * J - 1, I), rN = mgs_resid_at(Lf, p, f, P, 2 * J, I);
+    return -0.5 * (rS + rN);
+  }
+  const int j = 2 * J - 1, i = 2 * I - 1;
+  const double rSW = mgs_resid_at(Lf, p, f, P, j, i), rSE = mgs_resid_at(Lf, p, f, P, j, i + 1);
+  const double rNW = mgs_resid_at(Lf, p, f, P, j + 1, i), rNE = mgs_resid_at(Lf, p, f, P, j + 1, i + 1);
+  return -0.25 * ((rSW + rSE) + (rNW + rNE));
+}
+
+// inside the coarse grid and fluid
+__device__ __forceinline__ bool mgs_present(const MgsLevel* Lc, int J, int I) {
+  return J >= 1 && J <= Lc->ny && I >= 1 && I <= Lc->nx && mgs_fluid(Lc, J, I);
+}
+
+// correction of fluid fine cell (j, i): mgo_corr's formulas. A vertical or horizontal coarse neighbour
+// that is missing (solid, or beyond a Neumann side) takes the centre value c, the east ghost c g; a
+// missing diagonal the H value if V is missing, else the V value if H is missing, else c; an
+// east-ghost diagonal V' g.
+__device__ __forceinline__ double mgs_corr(const MgsLevel* Lc, int kind, const double* e, int pitch, int j, int i) {
+  const int dj = kind == MGO_X ? 0 : (j & 1) ? -1 : 1, di = kind == MGO_Y ? 0 : (i & 1) ? -1 : 1;
+  const int J = kind == MGO_X ? j : (j + 1) >> 1, I = kind == MGO_Y ? i : (i + 1) >> 1;
+  const double c = e[(size_t)J * pitch + I];
+  const bool Vp = mgs_present(Lc, J + dj, I);
+  const double V = Vp ? e[(size_t)(J + dj) * pitch + I] : c;
+  if (kind == MGO_Y) return (3.0 * c + V) * 0.25;
+  const bool east = I + di == Lc->nx + 1;
+  const bool Hp = mgs_present(Lc, J, I + di);
+  const double H = east ? c * Lc->g : Hp ? e[(size_t)J * pitch + I + di] : c;
+  if (kind == MGO_X) return (3.0 * c + H) * 0.25;
+  double D;
+  if (east) D = V * Lc->g;
+  else if (mgs_present(Lc, J + dj, I + di)) D = e[(size_t)(J + dj) * pitch + I + di];
+  else D = !Vp ? H : !Hp ? V : c;
+  return (((9.0 * c + 3.0 * V) + 3.0 * H) + D) * 0.0625;
+}
+
+// One colour of a sweep of level l, in place. Block: 4 rows x 128 columns, a lane one column pair and in
+// it the colour's cell. A's thread writes A and B (both from the values of before the launch).
+__global__ __launch_bounds__(256) void mgs_smooth_kernel(const MgsLevel* __restrict__ lv, int l, double* p,
+                                                         const double* __restrict__ f, int colour) {
+  const MgsLevel* L = lv + l;
+  const int nx = L->nx, ny = L->ny;
+  const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
+  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j > ny || gi > nx) return;
+  const int i = gi + ((j + colour) & 1);  // colour 0 holds the cells with i + j even
+  if (i < 1 || i > nx || !mgs_fluid(L, j, i) || mgs_is_b(L, j, i)) return;
+  const int P = L->pitch;
+  const size_t o = (size_t)j * P + i;
+  const double v = mgs_update(L, p + o, P, j, i, f[o], false);
+  if (mgs_is_a(L, j, i)) {
+    const size_t ob = o - P - 1;
+    const double vb = mgs_update(L, p + ob, P, j - 1, i - 1, f[ob], false);
+    p[ob] = vb;
+  }
+  p[o] = v;
+}
+
+// nsw (1..3) whole sweeps of level l in one launch, pin -> pout: mgo_smooth_tile_kernel's tile,
+// halo scheme and ownership. Only fluid cells are updated and written. The pair is a diagonal
+// dependency (Chebyshev distance 1): the halo's shrink of one cell per phase holds for it.
+__global__ __launch_bounds__(MG_TILE_THREADS) void mgs_smooth_tile_kernel(const MgsLevel* __restrict__ lv, int l,
+                                                                          const double* __restrict__ pin,
+                                                                          double* __restrict__ pout,
+                                                                          const double* __restrict__ f, int nsw) {
+  __shared__ double S[MG_TR * MG_TC];
+  const MgsLevel* L = lv + l;
+  const int nx = L->nx, ny = L->ny;
+  const int H = 2 * nsw, TW = MG_TC - 2 * H, TH = MG_TR - 2 * H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c0 = 2 * lane;
+  const int gx = (int)blockIdx.x * TW - H + c0;  // even (or negative: outside)
+  const int gy0 = (int)blockIdx.y * TH - H;
+  const size_t P = (size_t)L->pitch;
+  const bool colin = gx >= 0 && gx <= nx + 1;  // (gx + 1 <= nx + 2 < pitch)
+  double2 fr[MG_TQ];
+#pragma unroll
+  for (int q = 0; q < MG_TQ; ++q) {
+    const int r = w + 16 * q, gy = gy0 + r;
+    double2 v = make_double2(0.0, 0.0);
+    fr[q] = v;
+    if (colin && gy >= 0 && gy <= ny + 1) {
+      v = *reinterpret_cast<const double2*>(pin + (size_t)gy * P + gx);
+      fr[q] = *reinterpret_cast<const double2*>(f + (size_t)gy * P + gx);
+    }
+    *reinterpret_cast<double2*>(&S[r * MG_TC + c0]) = v;
+  }
+  __syncthreads();
+  for (int k = 0; k < 2 * nsw; ++k) {
+#pragma unroll
+    for (int q = 0; q < MG_TQ; ++q) {
+      const int r = w + 16 * q, gy = gy0 + r;
+      const int t = (gy + k) & 1;  // colour k & 1: the cells with i + j + colour even (gx is even)
+      const int c = c0 + t, i = gx + t;
+      if (gy < 1 || gy > ny || i < 1 || i > nx || !mgs_fluid(L, gy, i) || mgs_is_b(L, gy, i)) continue;
+      const int o = r * MG_TC + c;
+      const bool own = r > k && r < MG_TR - 1 - k && c > k && c < MG_TC - 1 - k;
+      // B = (r - 1, c - 1) by A's thread, under B's own condition (then A, at least k from the border, holds
+      // its value of before the phase; r - 1 > k >= 0 and c - 1 > k keep the cell and its neighbours inside)
+      const bool pair = mgs_is_a(L, gy, i) && r - 1 > k && r - 1 < MG_TR - 1 - k && c - 1 > k && c - 1 < MG_TC - 1 - k;
+      double v = 0.0, vb = 0.0;
+      if (own) v = mgs_update(L, S + o, MG_TC, gy, i, t ? fr[q].y : fr[q].x, false);
+      if (pair) vb = mgs_update(L, S + o - MG_TC - 1, MG_TC, gy - 1, i - 1, f[(size_t)(gy - 1) * P + (i - 1)], false);
+      if (own) S[o] = v;
+      if (pair) S[o - MG_TC - 1] = vb;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < MG_TQ; ++q) {
+    const int r = w + 16 * q, gy = gy0 + r;
+    if (r < H || r >= H + TH || c0 < H || c0 >= H + TW || gy < 1 || gy > ny) continue;  // (H, TW even: a pair is owned whole)
+    const double2 v = *reinterpret_cast<const double2*>(&S[r * MG_TC + c0]);
+    double* o = pout + (size_t)gy * P + gx;
+    const bool wa = gx >= 1 && gx <= nx && mgs_fluid(L, gy, gx), wb = gx + 1 >= 1 && gx + 1 <= nx && mgs_fluid(L, gy, gx + 1);
+    if (wa && wb) *reinterpret_cast<double2*>(o) = v;
+    else if (wa) o[0] = v.x;
+    else if (wb) o[1] = v.y;
+  }
+}
+
+// Residual of level l + restriction to level l + 1 by level l's kind; e_{l+1} = 0.
+// One thread per coarse cell; block: 4 coarse rows x 64 coarse columns.
+__global__ __launch_bounds__(256) void mgs_restrict_kernel(const MgsLevel* __restrict__ lv, int l,
+                                                           const double* __restrict__ p, const double* __restrict__ f,
+                                                           double* __restrict__ fc, double* __restrict__ ec) {
+  const MgsLevel* Lf = lv + l;
+  const MgsLevel* Lc = lv + l + 1;
+  const int I = 1 + blockIdx.x * 64 + (threadIdx.x & 63);
+  const int J = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (I > Lc->nx || J > Lc->ny) return;
+  const size_t oc = (size_t)J * Lc->pitch + I;
+  fc[oc] = mgs_restrict_cell(Lf, p, f, (size_t)Lf->pitch, J, I);
+  ec[oc] = 0.0;
+}
+
+// p_l += interpolant of e_{l+1} on the fluid cells. Block: 4 rows x 128 columns, a lane one aligned pair.
+__global__ __launch_bounds__(256) void mgs_prolong_kernel(const MgsLevel* __restrict__ lv, int l, double* __restrict__ p,
+                                                          const double* __restrict__ ec) {
+  const MgsLevel* L = lv + l;
+  const MgsLevel* Lc = lv + l + 1;
+  const int nx = L->nx, ny = L->ny, kind = L->kind;
+  const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
+  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j > ny || gi > nx) return;
+  const size_t o = (size_t)j * L->pitch + gi;
+  const int pc = Lc->pitch;
+  const bool wa = gi >= 1 && mgs_fluid(L, j, gi), wb = gi + 1 <= nx && mgs_fluid(L, j, gi + 1);
+  if (wa && wb) {
+    double2 v = *reinterpret_cast<const double2*>(p + o);
+    v.x += mgs_corr(Lc, kind, ec, pc, j, gi);
+    v.y += mgs_corr(Lc, kind, ec, pc, j, gi + 1);
+    *reinterpret_cast<double2*>(p + o) = v;
+  } else if (wa) {
+    p[o] += mgs_corr(Lc, kind, ec, pc, j, gi);
+  } else if (wb) {
+    p[o + 1] += mgs_corr(Lc, kind, ec, pc, j, gi + 1);
+  }
+}
+
+// one colour of a sweep of a level held in LDS (rows of nx + 2), by the whole workgroup
+__device__ __forceinline__ void mgs_tail_half_sweep(const MgsLevel* L, double* p, const double* f, int colour, bool sor) {
+  const int nx = L->nx, ny = L->ny, pitch = nx + 2, hw = (nx + 1) >> 1;
+  for (int q = threadIdx.x; q < ny * hw; q += MG_TAIL_THREADS) {
+    const int j = 1 + q / hw;
+    const int i = 1 + ((j + 1 + colour) & 1) + 2 * (q % hw);
+    if (i > nx || !mgs_fluid(L, j, i) || mgs_is_b(L, j, i)) continue;
+    const int o = j * pitch + i;
+    const double v = mgs_update(L, p + o, pitch, j, i, f[o], sor);
+    if (mgs_is_a(L, j, i)) {
+      const int ob = o - pitch - 1;
+      const double vb = mgs_update(L, p + ob, pitch, j - 1, i - 1, f[ob], sor);
+      p[ob] = vb;
+    }
+    p[o] = v;
+  }
+  __syncthreads();
+}
+
+// The sub-cycle over levels l0 .. last in one workgroup (mgo_tail_kernel's scheme).
+__global__ __launch_bounds__(MG_TAIL_THREADS) void mgs_tail_kernel(const MgsLevel* __restrict__ lv, int l0, int last,
+                                                                   int nu1, int nu2, const double* __restrict__ fg,
+                                                                   double* __restrict__ eg) {
+  __shared__ double S[MG_LDS_DOUBLES];
+  const int tid = threadIdx.x;
+  // every level's correction starts from zero, ghosts and solid cells included
+  for (int l = l0; l <= last; ++l) {
+    const MgsLevel* L = lv + l;
+    const int n = (L->nx + 2) * (L->ny + 2);
+    for (int q = tid; q < n; q += MG_TAIL_THREADS) S[L->lds_p + q] = 0.0;
+  }
+  {
+    const MgsLevel* L = lv + l0;
+    const int nx = L->nx;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      S[L->lds_f + j * (nx + 2) + i] = fg[(size_t)j * L->pitch + i];
+    }
+  }
+  __syncthreads();
+  for (int l = l0; l < last; ++l) {
+    const MgsLevel* L = lv + l;
+    const MgsLevel* Lc = L + 1;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    for (int s = 0; s < nu1; ++s) {
+      mgs_tail_half_sweep(L, p, f, 0, false);
+      mgs_tail_half_sweep(L, p, f, 1, false);
+    }
+    const int ncx = Lc->nx, pcp = ncx + 2;
+    for (int q = tid; q < ncx * Lc->ny; q += MG_TAIL_THREADS) {
+      const int J = 1 + q / ncx, I = 1 + q % ncx;
+      S[Lc->lds_f + J * pcp + I] = mgs_restrict_cell(L, p, f, (size_t)(L->nx + 2), J, I);
+    }
+    __syncthreads();
+  }
+  {
+    const MgsLevel* L = lv + last;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    for (int s = 0; s < L->coarse_sweeps; ++s) {
+      mgs_tail_half_sweep(L, p, f, 0, true);
+      mgs_tail_half_sweep(L, p, f, 1, true);
+    }
+  }
+  for (int l = last - 1; l >= l0; --l) {
+    const MgsLevel* L = lv + l;
+    const MgsLevel* Lc = L + 1;
+    double* p = S + L->lds_p;
+    const double* f = S + L->lds_f;
+    const double* e = S + Lc->lds_p;
+    const int nx = L->nx, pf = nx + 2, kind = L->kind;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      if (mgs_fluid(L, j, i)) p[j * pf + i] += mgs_corr(Lc, kind, e, Lc->nx + 2, j, i);
+    }
+    __syncthreads();
+    for (int s = 0; s < nu2; ++s) {
+      mgs_tail_half_sweep(L, p, f, 0, false);
+      mgs_tail_half_sweep(L, p, f, 1, false);
+    }
+  }
+  {
+    const MgsLevel* L = lv + l0;
+    const int nx = L->nx;
+    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
+      const int j = 1 + q / nx, i = 1 + q % nx;
+      eg[(size_t)j * L->pitch + i] = S[L->lds_p + j * (nx + 2) + i];
+    }
+  }
+}
+
+// The reference's ghost and solid refresh of level 0 (mg.hpp: mgs_refresh_launch). Thread t serves row t
+// (its west and east ghosts, its face-column cell) and column t (its south and north ghosts, its face-row
+// cell, the corner). The two ghosts that copy a face cell take its value of before this refresh, as the
+// reference's order gives it (ghost sides first): the thread that reads it from prev is the one that
+// then writes the cell in cur. The block is at least 2 columns wide and 2 rows high (the geometry rule).
+__global__ __launch_bounds__(256) void mgs_refresh_kernel(int nx, int ny, int P, int si, int jm, double* cur,
+                                                          const double* prev, const double* own) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int jb = jm + 1;
+  if (t >= 1 && t <= ny) {
+    const size_t o = (size_t)t * P;
+    cur[o] = t <= jm ? cur[o + 1] : t == jb ? prev[o + 1] : own[o + 1];
+    cur[o + nx + 1] = 0.0;
+    if (t == jb) cur[o + 1] = 0.0 + cur[o - P + 1];             // face row, column 1 (after its old value went west)
+    if (t > jb && t < ny) cur[o + si] = 0.0 + cur[o + si + 1];  // face column (row ny: by column si's thread)
+  }
+  if (t >= 1 && t <= nx) {
+    const size_t top = (size_t)(ny + 1) * P + t, row = (size_t)jb * P + t;
+    cur[t] = cur[(size_t)P + t];
+    cur[top] = t > si ? cur[top - P] : t == si ? prev[top - P] : own[top - P];
+    if (t == si) {
+      cur[top - P] = 0.0 + cur[top - P + 1];                     // face column, row ny
+      cur[row] = ((0.0 + cur[row + 1]) + cur[row - P]) * 0.5;    // the corner
+    }
+    if (t > 1 && t < si) cur[row] = 0.0 + cur[row - P];          // face row
+  }
+}
+
+__global__ __launch_bounds__(256) void mgs_copy_back_kernel(int nx, int ny, int P, int si, int jm, double* __restrict__ dst,
+                                                            const double* __restrict__ src) {
+  const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (i > nx + 1 || j > ny + 1) return;
+  if ((i == 0 || i == nx + 1) && (j == 0 || j == ny + 1)) return;  // corners: p's own
+  const bool solid = i >= 1 && i <= si && j > jm && j <= ny;
+  const bool face = j == jm + 1 || i == si;
+  if (solid && !face) return;  // interior solid cells: p's own
+  const size_t o = (size_t)j * P + i;
+  dst[o] = src[o];
+}
+
 }  // namespace
+
+void mgs_smooth_launch(const MgsLevel* dlv, const MgsLevel& L, int l, double* p, const double* f, int colour, void* stream) {
+  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
+  mgs_smooth_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, colour);
+}
+
+void mgs_smooth_tile_launch(const MgsLevel* dlv, const MgsLevel& L, int l, const double* pin, double* pout,
+                            const double* f, int nsw, void* stream) {
+  const int H = 2 * nsw;
+  const dim3 grid(L.nx / (MG_TC - 2 * H) + 1, L.ny / (MG_TR - 2 * H) + 1);
+  mgs_smooth_tile_kernel<<<grid, MG_TILE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, pin, pout, f, nsw);
+}
+
+void mgs_restrict_launch(const MgsLevel* dlv, const MgsLevel& Lc, int l, const double* p,
+                         const double* f, double* fc, double* ec, void* stream) {
+  const dim3 grid((Lc.nx + 63) / 64, (Lc.ny + 3) / 4);
+  mgs_restrict_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, fc, ec);
+}
+
+void mgs_prolong_launch(const MgsLevel* dlv, const MgsLevel& L, int l, double* p, const double* ec, void* stream) {
+  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
+  mgs_prolong_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, ec);
+}
+
+void mgs_tail_launch(const MgsLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream) {
+  mgs_tail_kernel<<<1, MG_TAIL_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l0, last, nu1, nu2, fg, eg);
+}
+
+void mgs_refresh_launch(const MgsLevel& L, double* cur, const double* prev, const double* own, void* stream) {
+  const int n = std::max(L.nx, L.ny) + 1;
+  mgs_refresh_kernel<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(L.nx, L.ny, L.pitch, L.si, L.jm, cur,
+                                                                                    prev, own);
+}
+
+void mgs_copy_back_launch(const MgsLevel& L, double* dst, const double* src, void* stream) {
+  const dim3 grid((L.nx + 2 + 63) / 64, (L.ny + 2 + 3) / 4);
+  mgs_copy_back_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(L.nx, L.ny, L.pitch, L.si, L.jm, dst, src);
+}
 
 void mgo_smooth_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* f, int colour, void* stream) {
   const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);

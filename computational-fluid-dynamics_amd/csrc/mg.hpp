@@ -110,4 +110,61 @@ void mgo_restrict_launch(const MgoLevel* dlv, const MgoLevel& Lc, int l, const d
 void mgo_prolong_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* ec, void* stream);
 void mgo_tail_launch(const MgoLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
 
+// ---------------------------------------------------------------- the step --
+// The third scheme (CFD_POISSON_MULTIGRID_STEP): the channel's
+// operator and semi-coarsening on the backwards-facing step's fluid cells
+// (backwards_step-01.cpp:872-939 on the ghosts and solids 685-740 refresh).
+// Level l has si = step_i >> a, jm = inlet_jmax >> b; cell (J, I) is fluid iff
+// I > si or J <= jm, and a neighbour exists only inside the grid and fluid.
+// Solid cells are no unknowns: never written, never read into a result. The
+// reference's corner solid (jm+1, si) = (p_A + p_B) / 2 couples its east fluid
+// cell A = (jm+1, si+1) and its south fluid cell B = (jm, si): eliminated, A's
+// west term is (cx/2)(p_B - p_A) and B's north term (cy/2)(p_A - p_B), on
+// every level. A and B have one colour; both updates of a phase use the
+// pre-phase values: A's thread forms both and writes both, B's own skips.
+// tests/mg_step_reference.py states every operation.
+struct MgsLevel {
+  int nx, ny;        // interior cells
+  int pitch;         // global memory: cell (j, i) at j * pitch + i (128-B aligned rows)
+  int lds_p, lds_f;  // one-launch tail: offsets (doubles) of p and f in LDS, rows of nx + 2 (-1: not in the tail)
+  int coarse_sweeps; // 4 max(nx, ny): SOR sweeps when this level is the coarsest
+  int kind;          // how this level is coarsened to the next: MGO_FULL / MGO_X / MGO_Y (-1: the coarsest)
+  int a, b;          // halvings of x and y down to this level
+  int si, jm;        // the block: solid iff i <= si and j > jm
+  double cx, cy;     // 1 / hx^2, 1 / hy^2
+  double chx, chy;   // cx / 2, cy / 2: A's west and B's north coefficient
+  double cE, g;      // east coefficient of column nx (cx / d); east ghost factor 1 - 1 / d of the prolongation
+  double rdiag[16];  // 1 / ((cw + ce) + (cs + cn)), index w | e << 1 | s << 2 | n << 3 (a set bit: that neighbour exists)
+  double rdA, rdB;   // the same for A (cw = chx) and B (cn = chy)
+  double one_m_omega;  // coarsest SOR: 1 - omega_c, omega_c = 2 / (1 + sin(pi / (max(nx, ny) + 1)))
+  double omr[16];      // omega_c * rdiag
+  double omrA, omrB;
+};
+
+struct MgsPlan {
+  int levels = 0;
+  int tail = 0;  // levels tail .. levels-1 run as one launch (tail >= 1)
+  MgsLevel lv[MG_MAX_LEVELS];
+};
+
+// The step's plan of a parameter block, or false with the rule that refused it in `why` (host only: params.cpp).
+bool mgs_make_plan(const cfd_params& p, MgsPlan& plan, std::string& why);
+
+// Launches (mg.hip), as the channel scheme's.
+void mgs_smooth_launch(const MgsLevel* dlv, const MgsLevel& L, int l, double* p, const double* f, int colour, void* stream);
+void mgs_smooth_tile_launch(const MgsLevel* dlv, const MgsLevel& L, int l, const double* pin, double* pout,
+                            const double* f, int nsw, void* stream);
+void mgs_restrict_launch(const MgsLevel* dlv, const MgsLevel& Lc, int l, const double* p,
+                         const double* f, double* fc, double* ec, void* stream);
+void mgs_prolong_launch(const MgsLevel* dlv, const MgsLevel& L, int l, double* p, const double* ec, void* stream);
+void mgs_tail_launch(const MgsLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
+// The reference's refresh (backwards_step-01.cpp:685-740) of level 0's field `cur` (row 0 of a buffer
+// with L's pitch): the four ghost sides, the block's face row (0 + south), corner (((0 + east) +
+// south) / 2) and face column (0 + east). Ghosts that copy a solid cell take an interior solid from
+// `own` (the solver's p: the only buffer that holds them) and a face cell's value of before this
+// refresh from `prev` (the buffer the previous refresh worked on).
+void mgs_refresh_launch(const MgsLevel& L, double* cur, const double* prev, const double* own, void* stream);
+// dst <- src over rows 0 .. ny+1 but for the four corner ghosts and the interior solid cells.
+void mgs_copy_back_launch(const MgsLevel& L, double* dst, const double* src, void* stream);
+
 }  // namespace cfd

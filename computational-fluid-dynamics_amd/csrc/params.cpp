@@ -217,7 +217,7 @@ int cfd::lexw_auto_sweeps(const cfd_params& p) {
 bool cfd::mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why) {
   if (p.case_id != CFD_CAVITY && p.case_id != CFD_RAYLEIGH_BENARD) {
     why = "multigrid covers the cavity and Rayleigh-Benard (case rule): the channel has CFD_POISSON_MULTIGRID_OPEN, "
-          "the step keeps SOR";
+          "the step CFD_POISSON_MULTIGRID_STEP";
     return false;
   }
   if (p.nx < 2 || p.ny < 2 || !(p.dx > 0)) {
@@ -311,7 +311,7 @@ extern "C" int cfd_mg_plan(const cfd_params* p, int* levels, int* coarse_nx, int
 bool cfd::mgo_make_plan(const cfd_params& p, MgoPlan& plan, std::string& why) {
   if (p.case_id != CFD_CHANNEL) {
     why = "open multigrid covers the channel (case rule): the cavity and Rayleigh-Benard have CFD_POISSON_MULTIGRID, "
-          "the step keeps SOR";
+          "the step CFD_POISSON_MULTIGRID_STEP";
     return false;
   }
   if (p.nx < 2 || p.ny < 2 || !(p.dx > 0) || !(p.dy > 0)) {
@@ -403,6 +403,137 @@ extern "C" int cfd_mg_open_plan(const cfd_params* p, int* levels, int* level_nx,
   cfd::MgoPlan plan;
   std::string why;
   if (!cfd::mgo_make_plan(*p, plan, why)) {
+    cfd::set_last_error(why);
+    return CFD_E_ARG;
+  }
+  if (levels) *levels = plan.levels;
+  for (int l = 0; l < cfd::MG_MAX_LEVELS; ++l) {
+    if (level_nx) level_nx[l] = l < plan.levels ? plan.lv[l].nx : 0;
+    if (level_ny) level_ny[l] = l < plan.levels ? plan.lv[l].ny : 0;
+  }
+  return CFD_OK;
+}
+
+// The step's plan (mg.hpp): the channel's semi-coarsening rule by
+// r = (hy / hx)^2 with the block halved with the grid, si = step_i >> a and jm =
+// inlet_jmax >> b. x can be halved while nx is even and at least 8 and si is even
+// and at least 2; y while ny is even and at least 8, jm is even and at least 2 and
+// the block is at least 2 rows high - so a coarse cell's children are all fluid or
+// all solid and every level keeps the pair A = (jm+1, si+1), B = (jm, si). The
+// constants are formed in the operations tests/mg_step_reference.py states.
+bool cfd::mgs_make_plan(const cfd_params& p, MgsPlan& plan, std::string& why) {
+  if (p.case_id != CFD_BACKSTEP) {
+    why = "step multigrid covers the backwards-facing step (case rule): the cavity and Rayleigh-Benard have "
+          "CFD_POISSON_MULTIGRID, the channel CFD_POISSON_MULTIGRID_OPEN";
+    return false;
+  }
+  if (p.nx < 2 || p.ny < 2 || !(p.dx > 0) || !(p.dy > 0)) {
+    why = "step multigrid needs a grid of at least 2 x 2 cells and dx, dy > 0 (grid rule)";
+    return false;
+  }
+  if (p.step_i < 2 || p.step_i >= p.nx || p.inlet_jmax < 2 || p.ny - p.inlet_jmax < 2) {
+    why = "step multigrid needs step_i >= 2, inlet_jmax >= 2 and a block at least 2 cells high (geometry rule): step_i " +
+          std::to_string(p.step_i) + ", inlet_jmax " + std::to_string(p.inlet_jmax) + " of " + std::to_string(p.ny) + " rows";
+    return false;
+  }
+  const std::string grid = "grid " + std::to_string(p.nx) + " x " + std::to_string(p.ny);
+  int nx = p.nx, ny = p.ny, a = 0, b = 0, si = p.step_i, jm = p.inlet_jmax, n = 0;
+  plan = MgsPlan{};
+  for (;;) {
+    if (n == MG_MAX_LEVELS) {
+      why = grid + " has no step multigrid plan (grid rule): more than " + std::to_string(MG_MAX_LEVELS) + " levels";
+      return false;
+    }
+    MgsLevel& L = plan.lv[n];
+    L.nx = nx;
+    L.ny = ny;
+    L.pitch = ((nx + 3) + 15) / 16 * 16;  // the solver's own row pitch rule (level 0: its p and f buffers)
+    L.lds_p = L.lds_f = -1;
+    L.a = a;
+    L.b = b;
+    L.si = si;
+    L.jm = jm;
+    const int m = std::max(nx, ny);
+    L.coarse_sweeps = 4 * m;
+    const double hx = std::ldexp(p.dx, a), hy = std::ldexp(p.dy, b);
+    L.cx = 1.0 / (hx * hx);
+    L.cy = 1.0 / (hy * hy);
+    L.chx = L.cx * 0.5;
+    L.chy = L.cy * 0.5;
+    const double d = 0.5 + std::ldexp(1.0, -(a + 1));
+    L.cE = L.cx / d;
+    L.g = 1.0 - 1.0 / d;
+    const double pi = 3.14159265358979323846;
+    const double omega = 2.0 / (1.0 + std::sin(pi / (m + 1)));
+    L.one_m_omega = 1.0 - omega;
+    for (int k = 0; k < 16; ++k) {
+      const double cw = (k & 1) ? L.cx : 0.0, ce = (k & 2) ? L.cx : L.cE;
+      const double cs = (k & 4) ? L.cy : 0.0, cn = (k & 8) ? L.cy : 0.0;
+      L.rdiag[k] = 1.0 / ((cw + ce) + (cs + cn));
+      L.omr[k] = omega * L.rdiag[k];
+    }
+    {  // A = (jm+1, si+1): west through the corner (cx / 2), south fluid; B = (jm, si): north through it (cy / 2), east fluid
+      const double ceA = si + 1 < nx ? L.cx : L.cE, cnA = jm + 1 < ny ? L.cy : 0.0;
+      L.rdA = 1.0 / ((L.chx + ceA) + (L.cy + cnA));
+      const double cwB = si > 1 ? L.cx : 0.0, ceB = si < nx ? L.cx : L.cE, csB = jm > 1 ? L.cy : 0.0;
+      L.rdB = 1.0 / ((cwB + ceB) + (csB + L.chy));
+      L.omrA = omega * L.rdA;
+      L.omrB = omega * L.rdB;
+    }
+    ++n;
+    const double q = hy / hx, r = q * q;
+    const bool can_x = nx % 2 == 0 && nx >= 8 && si % 2 == 0 && si >= 2;
+    const bool can_y = ny % 2 == 0 && ny >= 8 && jm % 2 == 0 && jm >= 2 && ny - jm >= 2;
+    L.kind = -1;
+    if (r > 2.0) {
+      if (can_x) L.kind = MGO_X;
+    } else if (r < 0.5) {
+      if (can_y) L.kind = MGO_Y;
+    } else if (can_x && can_y) {
+      L.kind = MGO_FULL;
+    }
+    if (L.kind < 0) break;
+    if (L.kind != MGO_Y) nx /= 2, si /= 2, ++a;
+    if (L.kind != MGO_X) ny /= 2, jm /= 2, ++b;
+  }
+  plan.levels = n;
+  const MgsLevel& C = plan.lv[n - 1];
+  if (n < 2) {
+    why = grid + " has no step multigrid plan (grid rule): the direction its spacings choose cannot be halved "
+                 "(a size must be even and at least 8, the block's edge even and at least 2)";
+    return false;
+  }
+  if ((long long)C.nx * C.ny > MG_COARSE_CELLS) {
+    why = grid + " has no step multigrid plan (grid rule): its coarsest level " + std::to_string(C.nx) + " x " +
+          std::to_string(C.ny) + " holds more than " + std::to_string(MG_COARSE_CELLS) + " cells";
+    return false;
+  }
+  int tail = n - 1;  // the one-launch tail, by mg_make_plan's rule
+  for (int l = n - 1; l >= 1; --l) {
+    long long need = 0;
+    for (int q = l; q < n; ++q) need += 2LL * (plan.lv[q].nx + 2) * (plan.lv[q].ny + 2);
+    if ((long long)plan.lv[l].nx * plan.lv[l].ny > MG_COARSE_CELLS || need > MG_LDS_DOUBLES) break;
+    tail = l;
+  }
+  plan.tail = tail;
+  int off = 0;
+  for (int q = tail; q < n; ++q) {
+    const int cells = (plan.lv[q].nx + 2) * (plan.lv[q].ny + 2);
+    plan.lv[q].lds_p = off;
+    plan.lv[q].lds_f = off + cells;
+    off += 2 * cells;
+  }
+  return true;
+}
+
+extern "C" int cfd_mg_step_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny) {
+  if (!p) {
+    cfd::set_last_error("null params");
+    return CFD_E_ARG;
+  }
+  cfd::MgsPlan plan;
+  std::string why;
+  if (!cfd::mgs_make_plan(*p, plan, why)) {
     cfd::set_last_error(why);
     return CFD_E_ARG;
   }

@@ -1707,6 +1707,10 @@ class Solver {
   bool mgo_on = false;
   MgoPlan mgop;
   MgoLevel* mgo_dlv = nullptr;
+  // CFD_POISSON_MULTIGRID_STEP, the backwards-facing step's scheme: its own plan and kernels (mgs_*), the buffers above
+  bool mgs_on = false;
+  MgsPlan mgsp;
+  MgsLevel* mgs_dlv = nullptr;
 
   void mg_release() noexcept {
     for (double* q : mg_p)
@@ -1726,6 +1730,9 @@ class Solver {
     if (mgo_dlv) (void)hipFree(mgo_dlv);
     mgo_dlv = nullptr;
     mgo_on = false;
+    if (mgs_dlv) (void)hipFree(mgs_dlv);
+    mgs_dlv = nullptr;
+    mgs_on = false;
     for (auto& e : mg_ev) {
       if (e) (void)hipEventDestroy(e);
       e = nullptr;
@@ -1741,7 +1748,8 @@ class Solver {
       return;
     }
     const bool open = method == CFD_POISSON_MULTIGRID_OPEN;  // the channel's scheme (mg.hpp "the channel")
-    if (method != CFD_POISSON_MULTIGRID && !open) throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
+    const bool stepm = method == CFD_POISSON_MULTIGRID_STEP;  // the step's scheme (mg.hpp "the step")
+    if (method != CFD_POISSON_MULTIGRID && !open && !stepm) throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
     if (S.size() != 1) throw Error(CFD_E_ARG, "multigrid runs on one strip (strip rule): this solver has n_strips > 1");
     if (comm) throw Error(CFD_E_ARG, "multigrid runs without ranks (rank rule): this is a rank solver");
     const int nu1 = opt && opt->pre_sweeps ? opt->pre_sweeps : 2, nu2 = opt && opt->post_sweeps ? opt->post_sweeps : 2;
@@ -1750,18 +1758,26 @@ class Solver {
       throw Error(CFD_E_ARG, "multigrid options: sweeps must be >= 0 with at least one per cycle, max_cycles >= 1");
     MgPlan plan;
     MgoPlan oplan;
+    MgsPlan splan;
     std::string why;
-    if (open ? !mgo_make_plan(P, oplan, why) : !mg_make_plan(P, plan, why)) throw Error(CFD_E_ARG, why);
-    if ((open ? oplan.lv[0].pitch : plan.lv[0].pitch) != pitch)
+    if (stepm ? !mgs_make_plan(P, splan, why) : open ? !mgo_make_plan(P, oplan, why) : !mg_make_plan(P, plan, why))
+      throw Error(CFD_E_ARG, why);
+    if ((stepm ? splan.lv[0].pitch : open ? oplan.lv[0].pitch : plan.lv[0].pitch) != pitch)
       throw Error(CFD_E_STATE, "multigrid plan pitch differs from the solver's");
-    const int levels = open ? oplan.levels : plan.levels, tail = open ? oplan.tail : plan.tail;
+    const int levels = stepm ? splan.levels : open ? oplan.levels : plan.levels;
+    const int tail = stepm ? splan.tail : open ? oplan.tail : plan.tail;
     auto level_bytes = [&](int l) {
-      return open ? (size_t)(oplan.lv[l].ny + 2) * oplan.lv[l].pitch * sizeof(double)
-                  : (size_t)(plan.lv[l].ny + 2) * plan.lv[l].pitch * sizeof(double);
+      return stepm  ? (size_t)(splan.lv[l].ny + 2) * splan.lv[l].pitch * sizeof(double)
+             : open ? (size_t)(oplan.lv[l].ny + 2) * oplan.lv[l].pitch * sizeof(double)
+                    : (size_t)(plan.lv[l].ny + 2) * plan.lv[l].pitch * sizeof(double);
     };
     HIPC(hipStreamSynchronize(st));
     mg_release();
-    if (open) {
+    if (stepm) {
+      mgsp = splan;
+      HIPC(hipMalloc(&mgs_dlv, sizeof(MgsLevel) * MG_MAX_LEVELS));
+      HIPC(hipMemcpy(mgs_dlv, mgsp.lv, sizeof(MgsLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
+    } else if (open) {
       mgop = oplan;
       HIPC(hipMalloc(&mgo_dlv, sizeof(MgoLevel) * MG_MAX_LEVELS));
       HIPC(hipMemcpy(mgo_dlv, mgop.lv, sizeof(MgoLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
@@ -1799,10 +1815,12 @@ class Solver {
     mg_nu2 = nu2;
     mg_max_cycles = mc;
     mgi.levels = levels;
-    mgi.coarse_nx = open ? oplan.lv[levels - 1].nx : plan.lv[levels - 1].nx;
-    mgi.coarse_ny = open ? oplan.lv[levels - 1].ny : plan.lv[levels - 1].ny;
-    mgi.coarse_sweeps = open ? oplan.lv[levels - 1].coarse_sweeps : plan.lv[levels - 1].coarse_sweeps;
-    (open ? mgo_on : mg_on) = true;
+    mgi.coarse_nx = stepm ? splan.lv[levels - 1].nx : open ? oplan.lv[levels - 1].nx : plan.lv[levels - 1].nx;
+    mgi.coarse_ny = stepm ? splan.lv[levels - 1].ny : open ? oplan.lv[levels - 1].ny : plan.lv[levels - 1].ny;
+    mgi.coarse_sweeps = stepm  ? splan.lv[levels - 1].coarse_sweeps
+                        : open ? oplan.lv[levels - 1].coarse_sweeps
+                               : plan.lv[levels - 1].coarse_sweeps;
+    (stepm ? mgs_on : open ? mgo_on : mg_on) = true;
   }
 
   // one V-cycle from level 0 on mg_cur[0] (p0: row 0 of the solver's p buffer) / f0; returns its launches
@@ -2034,7 +2052,127 @@ class Solver {
     }
   }
 
+  // The step's V-cycle (mgo_vcycle with the mgs_* launches).
+  int mgs_vcycle(double* p0, const double* f0) {
+    int launches = 0;
+    auto F_ = [&](int l) { return l == 0 ? f0 : (const double*)mg_f[l]; };
+    auto smooth = [&](int l, int n) {
+      if (mg_fused) {  // up to 3 sweeps per launch, into the level's other buffer
+        for (int left = n; left > 0;) {
+          const int k = left == 4 ? 2 : std::min(left, 3);
+          double* a = l == 0 ? p0 : mg_p[l];
+          double* other = mg_cur[l] == a ? mg_q[l] : a;
+          mgs_smooth_tile_launch(mgs_dlv, mgsp.lv[l], l, mg_cur[l], other, F_(l), k, st);
+          check_launch("mgs_smooth_tile");
+          ++launches;
+          mg_cur[l] = other;
+          left -= k;
+        }
+        return;
+      }
+      for (int q = 0; q < n; ++q)
+        for (int colour = 0; colour < 2; ++colour) {
+          mgs_smooth_launch(mgs_dlv, mgsp.lv[l], l, mg_cur[l], F_(l), colour, st);
+          check_launch("mgs_smooth");
+          ++launches;
+        }
+    };
+    const int tail = mgsp.tail, last = mgsp.levels - 1;
+    HIPC(hipEventRecord(mg_ev[0], st));
+    for (int l = 0; l < tail; ++l) {
+      smooth(l, mg_nu1);
+      mg_cur[l + 1] = mg_p[l + 1];
+      mgs_restrict_launch(mgs_dlv, mgsp.lv[l + 1], l, mg_cur[l], F_(l), mg_f[l + 1], mg_p[l + 1], st);
+      check_launch("mgs_restrict");
+      ++launches;
+      if (l == 0) HIPC(hipEventRecord(mg_ev[1], st));
+    }
+    mgs_tail_launch(mgs_dlv, tail, last, mg_nu1, mg_nu2, mg_f[tail], mg_p[tail], st);
+    check_launch("mgs_tail");
+    ++launches;
+    for (int l = tail - 1; l >= 0; --l) {
+      if (l == 0) HIPC(hipEventRecord(mg_ev[2], st));
+      mgs_prolong_launch(mgs_dlv, mgsp.lv[l], l, mg_cur[l], mg_cur[l + 1], st);
+      check_launch("mgs_prolong");
+      ++launches;
+      smooth(l, mg_nu2);
+    }
+    HIPC(hipEventRecord(mg_ev[3], st));
+    return launches;
+  }
+
+  // The step's solve (backwards_step-01.cpp:872-939 with a V-cycle for the sweep): a warm start from the
+  // field the solver holds, the loop primed with tol + 1, after each cycle the reference's ghost and
+  // solid refresh (685-740) and its own max-norm residual over the fluid cells.
+  void solve_mg_step(cfd_step_info* out) {
+    Strip& s = S[0];
+    double* X = s.b[pbuf(pcur)];
+    solve_tolerance();
+    const double tol = tol_host();
+    double* p0 = X + (size_t)(0 - s.g.row_lo) * pitch;
+    const double* f0 = s.b[B_F] + (size_t)(0 - s.g.row_lo) * pitch;
+    const int rrows = std::min(s.g.j1, P.ny) - std::max(s.g.j0, 1) + 1;
+    const dim3 rgrid((P.nx + 63) / 64, std::max(1, (rrows + 3) / 4));
+    HIPC(hipEventRecord(ev_a, st));
+    double res = tol + 1.0;  // backwards_step-01.cpp:890
+    int cycles = 0;
+    long long launches = 0;
+    double fine = 0.0;
+    mg_cur[0] = p0;
+    const double* prev = p0;  // the buffer whose face cells hold the last refresh (before the first: p's own)
+    while (res > tol && cycles < mg_max_cycles) {
+      launches += mgs_vcycle(p0, f0);
+      double* buf = mg_cur[0] == p0 ? X : mg_q0;
+      mgs_refresh_launch(mgsp.lv[0], mg_cur[0], prev, p0, st);
+      check_launch("mgs_refresh");
+      prev = mg_cur[0];
+      HIPC(hipMemsetAsync(resmax, 0, RES_SHARDS * SHARD_STRIDE * sizeof(double), st));
+      open_resmax_kernel<BACKSTEP><<<rgrid, 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax);
+      check_launch("resmax");
+      HIPC(hipMemcpyAsync(h_shard, resmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPC(hipStreamSynchronize(st));
+      res = 0.0;
+      for (int q = 0; q < RES_SHARDS; ++q) res = std::max(res, h_shard[q * SHARD_STRIDE]);
+      launches += 2;
+      ++cycles;
+      float a = 0.f, b = 0.f;
+      HIPC(hipEventElapsedTime(&a, mg_ev[0], mg_ev[1]));
+      HIPC(hipEventElapsedTime(&b, mg_ev[2], mg_ev[3]));
+      fine += (double)a + (double)b;
+    }
+    if (mg_cur[0] != p0) {
+      // an odd number of fused launches: the field is in the second buffer. Everything but the four
+      // corner ghosts and the interior solid cells, which stay p's own (the second buffer never held them).
+      mgs_copy_back_launch(mgsp.lv[0], p0, mg_cur[0], st);
+      check_launch("mgs_copy_back");
+      mg_cur[0] = p0;
+    }
+    HIPC(hipEventRecord(ev_b, st));
+    HIPC(hipEventSynchronize(ev_b));
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
+    const long long sweeps = (long long)cycles * (mg_nu1 + mg_nu2);
+    T.poisson_ms += ms;
+    T.poisson_launches += launches;
+    T.poisson_sweeps += sweeps;  // (level-0 sweeps)
+    T.poisson_cell_updates += (long long)P.nx * P.ny * sweeps;
+    mgi.solves += 1;
+    mgi.cycles += cycles;
+    mgi.launches += launches;
+    mgi.solve_ms += ms;
+    mgi.fine_ms += fine;
+    if (out) {
+      out->sor_iterations = cycles;
+      out->residual = res;
+    }
+  }
+
   void solve(cfd_step_info* out) {
+    if (mgs_on) {
+      T.sor_kernel = CFD_SOR_MULTIGRID;
+      solve_mg_step(out);
+      return;
+    }
     if (mgo_on) {
       T.sor_kernel = CFD_SOR_MULTIGRID;
       solve_mg_open(out);

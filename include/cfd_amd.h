@@ -181,7 +181,8 @@ enum cfd_sor_kernel {
 enum cfd_poisson_method {
   CFD_POISSON_SOR = 0,
   CFD_POISSON_MULTIGRID = 1,      /* the cavity and Rayleigh-Benard */
-  CFD_POISSON_MULTIGRID_OPEN = 2  /* the channel (below; added within ABI 14) */
+  CFD_POISSON_MULTIGRID_OPEN = 2, /* the channel (below; added within ABI 14) */
+  CFD_POISSON_MULTIGRID_STEP = 3  /* the backwards-facing step (below; added within ABI 14) */
 };
 typedef struct cfd_mg_options {
   int pre_sweeps, post_sweeps, max_cycles;  /* 0 (or a NULL options pointer): 2, 2, 50 */
@@ -219,6 +220,29 @@ int cfd_mg_plan(const cfd_params* p, int* levels, int* coarse_nx, int* coarse_ny
  * entries (unused entries 0); any pointer may be NULL.
  */
 int cfd_mg_open_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny);
+/*
+ * CFD_POISSON_MULTIGRID_STEP: the backwards-facing step's multigrid solve, a third
+ * method beside the other two - same options, same cfd_get_mg_info, cfd_timing.sor_kernel reports
+ * CFD_SOR_MULTIGRID, CFD_POISSON_SOR switches back. New symbols and one enum value within ABI 14.
+ *
+ * The step's operator (backwards_step-01.cpp:872-939) is the channel's over the fluid cells only:
+ * the cells of the solid block (i <= step_i and j > inlet_jmax) are no unknowns, and the block's
+ * corner solid, which the reference's refresh (685-740) sets to the mean of its east and its south
+ * fluid cell, is eliminated into those two cells' equations on every level. The solve starts from
+ * the pressure the solver holds and stops at tol = max(tol_factor * (max|source| over the fluid
+ * cells, or 1), abs_tol), tested on the reference's own residual after the reference's ghost and
+ * solid refresh; at least one cycle runs. Interior solid cells of p are left as they are. Levels are
+ * semi-coarsened by the channel's rule with the block halved with the grid: x can be halved while
+ * nx is even and >= 8 and the block's width is even and >= 2, y while ny is even and >= 8, the
+ * inlet's height is even and >= 2 and the block is at least 2 rows high. Valid with 2 .. 16 levels
+ * and a coarsest level of at most 4096 cells. Refusals (CFD_E_ARG, cfd_last_error naming the rule):
+ * the other cases (case rule: they have methods 1 and 2), step_i < 2, inlet_jmax < 2 or a block
+ * fewer than 2 cells high (geometry rule), a grid without a valid plan such as 472 x 108 (grid
+ * rule), more than one strip (strip rule), rank solvers (rank rule), bad options.
+ *
+ * cfd_mg_step_plan (host only): as cfd_mg_open_plan.
+ */
+int cfd_mg_step_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny);
 
 /* Library / ABI info. */
 int cfd_abi_version(void);

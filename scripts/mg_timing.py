@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Timing of the multigrid pressure solve beside the default (SOR) solve.
 
-For each grid (--case cavity or channel, Re = 1000 unless --re) in one process on
-one device (the channel: --method multigrid-open, its default):
+For each grid (--case cavity, channel or step, Re = 1000 unless --re; the step: 400,
+BASELINE configs[3]) in one process on one device (the channel: --method
+multigrid-open, the step: multigrid-step, their defaults):
   * the default solve (the reference's SOR, which stops at its 10000-sweep cap
     at these sizes): HIP-event ms per solve, sweeps, final residual, tolerance;
   * the multigrid solve V(2,2): ms per solve, cycles, launches, ms per cycle
@@ -19,8 +20,9 @@ JSON file per grid under --out.
 
   python scripts/mg_timing.py --sizes 1024x1024 4096x4096 992x992 --out profiles/mg --commit <hash>
   python scripts/mg_timing.py --case channel --sizes 4096x512 1024x128 --out profiles/mg --commit <hash>
+  python scripts/mg_timing.py --case step --sizes 256x32 1024x128 8192x512 --out profiles/mg --commit <hash>
 
-The channel's run fails (exit 1) if a multigrid solve ends above its tolerance.
+The channel's and the step's run fails (exit 1) if a multigrid solve ends above its tolerance.
 """
 from __future__ import annotations
 
@@ -51,7 +53,11 @@ def level0_rate(fine_ms_per_cycle, bytes_per_cell, cells):
 
 
 def tolerance(cp, src):
-    m = float(np.abs(src[1:-1, 1:-1]).max())
+    a = np.abs(src[1:-1, 1:-1])
+    if cp.case_id == C.BACKSTEP:  # over the fluid cells (backwards_step-01.cpp:879-888)
+        i, j = np.arange(1, cp.nx + 1)[None, :], np.arange(1, cp.ny + 1)[:, None]
+        a = a[(i > cp.step_i) | (j <= cp.inlet_jmax)]
+    m = float(a.max())
     if cp.case_id == C.CAVITY:
         return cp.tol_factor * m
     return max(cp.tol_factor * (m if m > 0 else 1.0), cp.abs_tol)  # channel-01.cpp:642-649
@@ -86,12 +92,12 @@ def run(cp, steps, warmup, **kw):
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--case", choices=["cavity", "channel"], default="cavity")
-    ap.add_argument("--method", choices=["multigrid", "multigrid-open"], default=None,
-                    help="default: multigrid for the cavity, multigrid-open for the channel")
-    ap.add_argument("--re", type=float, default=1000.0)
+    ap.add_argument("--case", choices=["cavity", "channel", "step"], default="cavity")
+    ap.add_argument("--method", choices=["multigrid", "multigrid-open", "multigrid-step"], default=None,
+                    help="default: multigrid for the cavity, multigrid-open for the channel, multigrid-step for the step")
+    ap.add_argument("--re", type=float, default=None, help="default: 1000; the step: 400")
     ap.add_argument("--sizes", nargs="+", default=None, help="default: 1024x1024 4096x4096 992x992 (cavity), "
-                    "4096x512 1024x128 (channel)")
+                    "4096x512 1024x128 (channel), 256x32 1024x128 8192x512 (step)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mg"))
@@ -99,12 +105,15 @@ def main() -> int:
     ap.add_argument("--skip-default", action="store_true", help="leave the default (SOR) solve out")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
-    method = a.method or ("multigrid" if a.case == "cavity" else "multigrid-open")
-    sizes = a.sizes or (["1024x1024", "4096x4096", "992x992"] if a.case == "cavity" else ["4096x512", "1024x128"])
+    method = a.method or {"cavity": "multigrid", "channel": "multigrid-open", "step": "multigrid-step"}[a.case]
+    sizes = a.sizes or {"cavity": ["1024x1024", "4096x4096", "992x992"], "channel": ["4096x512", "1024x128"],
+                        "step": ["256x32", "1024x128", "8192x512"]}[a.case]
+    if a.re is None:
+        a.re = 400.0 if a.case == "step" else 1000.0
     ok = True
     for size in sizes:
         nx, ny = (int(v) for v in size.split("x"))
-        cp = C.make_params(a.case, re=a.re, nx=nx, ny=ny)
+        cp = C.make_params("backwards_step" if a.case == "step" else a.case, re=a.re, nx=nx, ny=ny)
         rec = dict(case=a.case, method=method, re=a.re, nx=nx, ny=ny, steps=a.steps, warmup=a.warmup, commit=a.commit,
                    timer="HIP events (cfd_timing.poisson_ms, cfd_mg_info.solve_ms / fine_ms)")
         rec["multigrid_v22"] = v22 = run(cp, a.steps, a.warmup, poisson=method)
@@ -116,7 +125,7 @@ def main() -> int:
         rec["level0_colour_launches"] = f1 = level0_rate(c22["fine_ms_per_cycle"], COLOUR_BYTES_PER_CELL, cells)
         if not a.skip_default:
             rec["default_sor"] = run(cp, a.steps, a.warmup)
-        if a.case == "channel" and not (all(v22["converged"]) and all(c22["converged"])):
+        if a.case != "cavity" and not (all(v22["converged"]) and all(c22["converged"])):
             ok = False
             print(f"{nx}x{ny}: a multigrid solve ended above its tolerance", file=sys.stderr)
         path = os.path.join(a.out, f"mg_timing_{a.case}_{nx}x{ny}.json")
