@@ -323,22 +323,23 @@ def mg_plan(params: CaseParams) -> tuple[int, int, int]:
     return lv.value, cx.value, cy.value
 
 
+def _mg_level_sizes(name: str, params: CaseParams) -> list[tuple[int, int]]:
+    cp = to_cparams(params)
+    lv, ax, ay = ctypes.c_int(), (ctypes.c_int * 16)(), (ctypes.c_int * 16)()
+    _lib.check(getattr(_lib.lib(), name)(ctypes.byref(cp), ctypes.byref(lv), ax, ay), name)
+    return [(ax[l], ay[l]) for l in range(lv.value)]
+
+
 def mg_open_plan(params: CaseParams) -> list[tuple[int, int]]:
     """cfd_mg_open_plan (host only): [(nx, ny)] of every level of the channel's multigrid
     plan of these parameters; raises CfdError naming the rule where there is none."""
-    cp = to_cparams(params)
-    lv, ax, ay = ctypes.c_int(), (ctypes.c_int * 16)(), (ctypes.c_int * 16)()
-    _lib.check(_lib.lib().cfd_mg_open_plan(ctypes.byref(cp), ctypes.byref(lv), ax, ay), "cfd_mg_open_plan")
-    return [(ax[l], ay[l]) for l in range(lv.value)]
+    return _mg_level_sizes("cfd_mg_open_plan", params)
 
 
 def mg_step_plan(params: CaseParams) -> list[tuple[int, int]]:
     """cfd_mg_step_plan (host only): [(nx, ny)] of every level of the backwards-facing step's
     multigrid plan of these parameters; raises CfdError naming the rule where there is none."""
-    cp = to_cparams(params)
-    lv, ax, ay = ctypes.c_int(), (ctypes.c_int * 16)(), (ctypes.c_int * 16)()
-    _lib.check(_lib.lib().cfd_mg_step_plan(ctypes.byref(cp), ctypes.byref(lv), ax, ay), "cfd_mg_step_plan")
-    return [(ax[l], ay[l]) for l in range(lv.value)]
+    return _mg_level_sizes("cfd_mg_step_plan", params)
 
 
 def params_from_library_rb(ra: float, pr: float, nx: int = 0, ny: int = 0, dt: float = 0.0) -> _lib.CfdParams:

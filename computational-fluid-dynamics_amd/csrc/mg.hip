@@ -8,24 +8,22 @@
 // (mg_smooth_tile_kernel); the plain form is one launch per colour, in place
 // (mg_smooth_kernel: a colour's cells read only the other colour's, so no
 // launch reads what it writes), kept for comparison. The residual is
-// formed inside the restriction (four children per coarse cell) and the
+// formed inside the restriction (the children of a coarse cell) and the
 // coarse correction's ghost layer inside the prolongation, so neither goes to
 // memory. From the first level whose cells fit one workgroup's LDS down, the
 // whole sub-cycle - smoothing, restriction, the coarsest level's SOR sweeps,
 // prolongation - is one launch of one workgroup (mg_tail_kernel): those levels
 // are launch-bound, and the arithmetic is the same per-cell functions.
 //
-// Operand order (tests/mg_reference.py, cavity-01.cpp:651-654, 670-673): the
-// indicator products are real multiplies on boundary cells (0 * x keeps x's
-// sign, as in the reference); interior cells skip them (1 * x == x), the same
-// bits. The library builds with -ffp-contract=off: no fused multiply-adds.
-//
-// The second half of the file (mgo_*) is the channel's scheme: the same
-// launches with an anisotropic, semi-coarsened operator and a Dirichlet zero
-// in the east ghost column (tests/mg_open_reference.py). The third part
-// (mgs_*) is the backwards-facing step's: the channel's operator over the
-// fluid cells only, the block's corner coupling eliminated into its two fluid
-// neighbours (tests/mg_step_reference.py).
+// Every kernel is one template over a scheme: a struct of static per-cell
+// functions over its level type (mg.hpp) - the update of a cell, the coarse
+// source of a coarse cell, the correction of a fine cell, whether a cell is an
+// unknown. The file states the three schemes' cell functions first (the
+// cavity's mg_*, the channel's mgo_*, the step's mgs_*, each in the operand
+// order of its restatement under tests/), then the kernels, then the launches.
+// What only the step needs - the fluid tests and the coupled pair A / B - sits
+// behind `if constexpr (S::has_pair)` or folds away with S::unknown.
+// The library builds with -ffp-contract=off: no fused multiply-adds.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +33,14 @@
 namespace cfd {
 
 namespace {
+
+constexpr int MG_TR = 64, MG_TC = 128, MG_TILE_THREADS = 1024, MG_TQ = MG_TR / 16;  // the smoothing tile (below)
+
+// ============================================================= the cavity ==
+// Operand order (tests/mg_reference.py, cavity-01.cpp:651-654, 670-673): the
+// indicator products are real multiplies on boundary cells (0 * x keeps x's
+// sign, as in the reference); interior cells skip them (1 * x == x), the same
+// bits.
 
 __device__ __forceinline__ bool mg_interior(const MgLevel* L, int j, int i) {
   return i > 1 && i < L->nx && j > 1 && j < L->ny;
@@ -111,244 +117,52 @@ __device__ __forceinline__ double mg_corr(const MgLevel* Lc, const double* e, in
   return (((9.0 * c + 3.0 * V) + 3.0 * H) + D) * 0.0625;
 }
 
-// ------------------------------------------------------ multi-launch levels --
-
-// One colour of a sweep of level l. Block: 4 waves = 4 rows x 128 columns.
-__global__ __launch_bounds__(256) void mg_smooth_kernel(const MgLevel* __restrict__ lv, int l, double* p,
-                                                        const double* __restrict__ f, int colour) {
-  const MgLevel* L = lv + l;
-  const int nx = L->nx, ny = L->ny;
-  const int lane = threadIdx.x & 63;
-  const int gi = blockIdx.x * 128 + 2 * lane;  // even: a 16-B aligned pair
-  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (j > ny || gi > nx) return;
-  const int t = (j + colour) & 1;  // colour 0 holds the cells with i + j even: component t of the pair
-  const int i = gi + t;
-  if (i < 1 || i > nx) return;
-  const size_t P = (size_t)L->pitch, o = (size_t)j * P + gi;
-  const double2 pc = *reinterpret_cast<const double2*>(p + o);
-  const double2 ps = *reinterpret_cast<const double2*>(p + o - P);
-  const double2 pn = *reinterpret_cast<const double2*>(p + o + P);
-  const double2 fc = *reinterpret_cast<const double2*>(f + o);
-  double v;
-  if (t == 0) v = mg_relax(L, j, i, p[o - 1], pc.y, ps.x, pn.x, fc.x);  // (i >= 2: o - 1 is column i - 1 >= 1)
-  else v = mg_relax(L, j, i, pc.x, p[o + 2], ps.y, pn.y, fc.y);        // (o + 2: column i + 1 <= nx + 1 < pitch)
-  p[o + t] = v;
-}
-
-// nsw (1..3) whole sweeps of level l in one launch, pin -> pout (as tile.hip
-// does for SOR). A workgroup of 16 waves holds a region of MG_TR rows x 128
-// columns of p in LDS: its tile plus H = 2 nsw cells of halo on every side,
-// since each colour phase leaves one more ring next to the region's border
-// stale. Phase k (colour k & 1 of sweep k >> 1) updates the cells at least
-// k + 1 from the border; after 2 nsw phases the tile itself (margin H) holds
-// what the sweeps over the whole level give - the halo cells are recomputed by
-// the neighbouring workgroups, same operands, same bits. p and f are read
-// once (1.2x with the halos) and p written once: 24-28 B per cell for nsw
-// sweeps where the colour launches move up to 48 per sweep. Lane l owns the
-// aligned column pair (2l, 2l + 1) of rows w, w + 16, ... and keeps their f
-// in registers; region column c is global column bx TW - H + c (even offset:
-// the pairs stay 16-B aligned), region row r global row by TH - H + r.
-constexpr int MG_TR = 64, MG_TC = 128, MG_TILE_THREADS = 1024, MG_TQ = MG_TR / 16;
-__global__ __launch_bounds__(MG_TILE_THREADS) void mg_smooth_tile_kernel(const MgLevel* __restrict__ lv, int l,
-                                                                         const double* __restrict__ pin,
-                                                                         double* __restrict__ pout,
-                                                                         const double* __restrict__ f, int nsw) {
-  __shared__ double S[MG_TR * MG_TC];
-  const MgLevel* L = lv + l;
-  const int nx = L->nx, ny = L->ny;
-  const int H = 2 * nsw, TW = MG_TC - 2 * H, TH = MG_TR - 2 * H;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c0 = 2 * lane;
-  const int gx = (int)blockIdx.x * TW - H + c0;  // even (or negative: outside)
-  const int gy0 = (int)blockIdx.y * TH - H;
-  const size_t P = (size_t)L->pitch;
-  const bool colin = gx >= 0 && gx <= nx + 1;  // (gx + 1 <= nx + 2 < pitch)
-  double2 fr[MG_TQ];
-#pragma unroll
-  for (int q = 0; q < MG_TQ; ++q) {
-    const int r = w + 16 * q, gy = gy0 + r;
-    double2 v = make_double2(0.0, 0.0);
-    fr[q] = v;
-    if (colin && gy >= 0 && gy <= ny + 1) {
-      v = *reinterpret_cast<const double2*>(pin + (size_t)gy * P + gx);
-      fr[q] = *reinterpret_cast<const double2*>(f + (size_t)gy * P + gx);
-    }
-    *reinterpret_cast<double2*>(&S[r * MG_TC + c0]) = v;
+// What a scheme supplies to the kernels (the other two below alike). A field is a pointer with rows of P
+// doubles, global memory or LDS.
+struct MgCavity {
+  using Level = MgLevel;
+  static constexpr bool has_pair = false;   // no coupled pair of cells A / B
+  static constexpr bool pair_loads = true;  // the colour launch reads aligned double2 pairs
+  // whether cell (j, i) inside the grid is an unknown
+  static __device__ __forceinline__ bool unknown(const Level*, int, int) { return true; }
+  static __device__ __forceinline__ double relax(const Level* L, int j, int i, double pW, double pE, double pS, double pN,
+                                                 double f) {
+    return mg_relax(L, j, i, pW, pE, pS, pN, f);
   }
-  __syncthreads();
-  for (int k = 0; k < 2 * nsw; ++k) {
+  // the update of cell (j, i), p pointing at it: Gauss-Seidel, or the coarsest level's SOR
+  static __device__ __forceinline__ double update(const Level* L, const double* p, int P, int j, int i, double f, bool sor) {
+    return sor ? mg_sor(L, j, i, p[0], p[-1], p[1], p[-P], p[P], f) : mg_relax(L, j, i, p[-1], p[1], p[-P], p[P], f);
+  }
+  // the source of cell (J, I) of level Lf + 1 from Lf's fields. Global rows are 128-B aligned and column
+  // 2I - 2 even: two aligned pairs per row; LDS rows of nx + 2 doubles are not 16-B aligned: scalar loads.
+  template <bool Aligned>
+  static __device__ __forceinline__ double coarse_source(const Level* Lf, const double* p, const double* f, size_t P, int J,
+                                                         int I) {
+    const size_t o = (size_t)(2 * J - 2) * P + (size_t)(2 * I - 2);
+    double a[4][4];
 #pragma unroll
-    for (int q = 0; q < MG_TQ; ++q) {
-      const int r = w + 16 * q, gy = gy0 + r;
-      const int t = (gy + k) & 1;  // colour k & 1: the cells with i + j + colour even (gx is even)
-      const int c = c0 + t, i = gx + t;
-      if (r > k && r < MG_TR - 1 - k && c > k && c < MG_TC - 1 - k && gy >= 1 && gy <= ny && i >= 1 && i <= nx) {
-        const int o = r * MG_TC + c;
-        S[o] = mg_relax(L, gy, i, S[o - 1], S[o + 1], S[o - MG_TC], S[o + MG_TC], t ? fr[q].y : fr[q].x);
+    for (int r = 0; r < 4; ++r) {
+      if constexpr (Aligned) {
+        const double2 lo = *reinterpret_cast<const double2*>(p + o + r * P);
+        const double2 hi = *reinterpret_cast<const double2*>(p + o + r * P + 2);
+        a[r][0] = lo.x, a[r][1] = lo.y, a[r][2] = hi.x, a[r][3] = hi.y;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[r][c] = p[o + r * P + c];
       }
     }
-    __syncthreads();
+    return mg_restrict_cell(Lf, J, I, a, f[o + P + 1], f[o + P + 2], f[o + 2 * P + 1], f[o + 2 * P + 2]);
   }
-#pragma unroll
-  for (int q = 0; q < MG_TQ; ++q) {
-    const int r = w + 16 * q, gy = gy0 + r;
-    if (r < H || r >= H + TH || c0 < H || c0 >= H + TW || gy < 1 || gy > ny) continue;  // (H, TW even: a pair is owned whole)
-    const double2 v = *reinterpret_cast<const double2*>(&S[r * MG_TC + c0]);
-    double* o = pout + (size_t)gy * P + gx;
-    if (gx >= 1 && gx + 1 <= nx) *reinterpret_cast<double2*>(o) = v;
-    else if (gx >= 1 && gx <= nx) o[0] = v.x;
-    else if (gx + 1 >= 1 && gx + 1 <= nx) o[1] = v.y;
+  // the correction of cell (j, i) of level L from e of level L + 1 (rows of `pitch` doubles)
+  static __device__ __forceinline__ double corr(const Level* L, const double* e, int pitch, int j, int i) {
+    return mg_corr(L + 1, e, pitch, j, i);
   }
-}
-
-// Residual of level l + full-weighting restriction to level l + 1; e_{l+1} = 0.
-// One thread per coarse cell; block: 4 coarse rows x 64 coarse columns.
-__global__ __launch_bounds__(256) void mg_restrict_kernel(const MgLevel* __restrict__ lv, int l,
-                                                          const double* __restrict__ p, const double* __restrict__ f,
-                                                          double* __restrict__ fc, double* __restrict__ ec) {
-  const MgLevel* Lf = lv + l;
-  const MgLevel* Lc = lv + l + 1;
-  const int I = 1 + blockIdx.x * 64 + (threadIdx.x & 63);
-  const int J = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (I > Lc->nx || J > Lc->ny) return;
-  const size_t P = (size_t)Lf->pitch;
-  const size_t o = (size_t)(2 * J - 2) * P + (size_t)(2 * I - 2);  // even column: two aligned pairs per row
-  double a[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const double2 lo = *reinterpret_cast<const double2*>(p + o + r * P);
-    const double2 hi = *reinterpret_cast<const double2*>(p + o + r * P + 2);
-    a[r][0] = lo.x, a[r][1] = lo.y, a[r][2] = hi.x, a[r][3] = hi.y;
-  }
-  const double fSW = f[o + P + 1], fSE = f[o + P + 2], fNW = f[o + 2 * P + 1], fNE = f[o + 2 * P + 2];
-  const size_t oc = (size_t)J * Lc->pitch + I;
-  fc[oc] = mg_restrict_cell(Lf, J, I, a, fSW, fSE, fNW, fNE);
-  ec[oc] = 0.0;
-}
-
-// p_l += interpolant of e_{l+1}. Block: 4 rows x 128 columns, a lane one aligned pair.
-__global__ __launch_bounds__(256) void mg_prolong_kernel(const MgLevel* __restrict__ lv, int l, double* __restrict__ p,
-                                                         const double* __restrict__ ec) {
-  const MgLevel* L = lv + l;
-  const MgLevel* Lc = lv + l + 1;
-  const int nx = L->nx, ny = L->ny;
-  const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
-  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (j > ny || gi > nx) return;
-  const size_t o = (size_t)j * L->pitch + gi;
-  const int pc = Lc->pitch;
-  if (gi >= 1 && gi + 1 <= nx) {
-    double2 v = *reinterpret_cast<const double2*>(p + o);
-    v.x += mg_corr(Lc, ec, pc, j, gi);
-    v.y += mg_corr(Lc, ec, pc, j, gi + 1);
-    *reinterpret_cast<double2*>(p + o) = v;
-  } else if (gi >= 1) {
-    p[o] += mg_corr(Lc, ec, pc, j, gi);  // (gi == nx)
-  } else {
-    p[o + 1] += mg_corr(Lc, ec, pc, j, 1);  // (gi == 0; nx >= 2)
-  }
-}
-
-// ------------------------------------------------------- one-launch tail --
-
-// one colour of a sweep of a level held in LDS (rows of nx + 2), by the whole workgroup
-__device__ __forceinline__ void tail_half_sweep(const MgLevel* L, double* p, const double* f, int colour, bool sor) {
-  const int nx = L->nx, ny = L->ny, pitch = nx + 2, hw = (nx + 1) >> 1;
-  for (int q = threadIdx.x; q < ny * hw; q += MG_TAIL_THREADS) {
-    const int j = 1 + q / hw;
-    const int i = 1 + ((j + 1 + colour) & 1) + 2 * (q % hw);
-    if (i > nx) continue;
-    const int o = j * pitch + i;
-    p[o] = sor ? mg_sor(L, j, i, p[o], p[o - 1], p[o + 1], p[o - pitch], p[o + pitch], f[o])
-               : mg_relax(L, j, i, p[o - 1], p[o + 1], p[o - pitch], p[o + pitch], f[o]);
-  }
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(MG_TAIL_THREADS) void mg_tail_kernel(const MgLevel* __restrict__ lv, int l0, int last,
-                                                                  int nu1, int nu2, const double* __restrict__ fg,
-                                                                  double* __restrict__ eg) {
-  __shared__ double S[MG_LDS_DOUBLES];
-  const int tid = threadIdx.x;
-  // every level's correction starts from zero, ghosts included
-  for (int l = l0; l <= last; ++l) {
-    const MgLevel* L = lv + l;
-    const int n = (L->nx + 2) * (L->ny + 2);
-    for (int q = tid; q < n; q += MG_TAIL_THREADS) S[L->lds_p + q] = 0.0;
-  }
-  {
-    const MgLevel* L = lv + l0;
-    const int nx = L->nx;
-    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
-      const int j = 1 + q / nx, i = 1 + q % nx;
-      S[L->lds_f + j * (nx + 2) + i] = fg[(size_t)j * L->pitch + i];
-    }
-  }
-  __syncthreads();
-  for (int l = l0; l < last; ++l) {
-    const MgLevel* L = lv + l;
-    const MgLevel* Lc = L + 1;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
-    for (int s = 0; s < nu1; ++s) {
-      tail_half_sweep(L, p, f, 0, false);
-      tail_half_sweep(L, p, f, 1, false);
-    }
-    const int pf = L->nx + 2, ncx = Lc->nx, pcp = ncx + 2;
-    for (int q = tid; q < ncx * Lc->ny; q += MG_TAIL_THREADS) {
-      const int J = 1 + q / ncx, I = 1 + q % ncx;
-      const int o = (2 * J - 2) * pf + 2 * I - 2;
-      double a[4][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) a[r][c] = p[o + r * pf + c];
-      S[Lc->lds_f + J * pcp + I] =
-          mg_restrict_cell(L, J, I, a, f[o + pf + 1], f[o + pf + 2], f[o + 2 * pf + 1], f[o + 2 * pf + 2]);
-    }
-    __syncthreads();
-  }
-  {
-    const MgLevel* L = lv + last;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
-    for (int s = 0; s < L->coarse_sweeps; ++s) {
-      tail_half_sweep(L, p, f, 0, true);
-      tail_half_sweep(L, p, f, 1, true);
-    }
-  }
-  for (int l = last - 1; l >= l0; --l) {
-    const MgLevel* L = lv + l;
-    const MgLevel* Lc = L + 1;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
-    const double* e = S + Lc->lds_p;
-    const int nx = L->nx, pf = nx + 2;
-    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
-      const int j = 1 + q / nx, i = 1 + q % nx;
-      p[j * pf + i] += mg_corr(Lc, e, Lc->nx + 2, j, i);
-    }
-    __syncthreads();
-    for (int s = 0; s < nu2; ++s) {
-      tail_half_sweep(L, p, f, 0, false);
-      tail_half_sweep(L, p, f, 1, false);
-    }
-  }
-  {
-    const MgLevel* L = lv + l0;
-    const int nx = L->nx;
-    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
-      const int j = 1 + q / nx, i = 1 + q % nx;
-      eg[(size_t)j * L->pitch + i] = S[L->lds_p + j * (nx + 2) + i];
-    }
-  }
-}
+};
 
 // ============================================================ the channel ==
-// The second scheme (mg.hpp "the channel", tests/mg_open_reference.py): the
-// same streams and the same tile, halo and tail schemes with the anisotropic
-// cell functions below. A neighbour a cell does not have is skipped by a
+// The second scheme (mg.hpp "the channel", tests/mg_open_reference.py): an
+// anisotropic, semi-coarsened operator with a Dirichlet zero in the east ghost
+// column. A neighbour a cell does not have is skipped by a
 // select on the cell's mask (bit set: the neighbour exists), never multiplied
 // by 0, so the ghost cells - which hold the reference's refreshed values at
 // level 0 and nothing in particular elsewhere - reach no result.
@@ -445,221 +259,34 @@ __device__ __forceinline__ double mgo_corr(const MgoLevel* Lc, int kind, const d
   return (((9.0 * c + 3.0 * V) + 3.0 * H) + D) * 0.0625;
 }
 
-// One colour of a sweep of level l (mg_smooth_kernel's layout). Block: 4 waves = 4 rows x 128 columns.
-__global__ __launch_bounds__(256) void mgo_smooth_kernel(const MgoLevel* __restrict__ lv, int l, double* p,
-                                                         const double* __restrict__ f, int colour) {
-  const MgoLevel* L = lv + l;
-  const int nx = L->nx, ny = L->ny;
-  const int lane = threadIdx.x & 63;
-  const int gi = blockIdx.x * 128 + 2 * lane;  // even: a 16-B aligned pair
-  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (j > ny || gi > nx) return;
-  const int t = (j + colour) & 1;  // colour 0 holds the cells with i + j even: component t of the pair
-  const int i = gi + t;
-  if (i < 1 || i > nx) return;
-  const size_t P = (size_t)L->pitch, o = (size_t)j * P + gi;
-  const double2 pc = *reinterpret_cast<const double2*>(p + o);
-  const double2 ps = *reinterpret_cast<const double2*>(p + o - P);
-  const double2 pn = *reinterpret_cast<const double2*>(p + o + P);
-  const double2 fc = *reinterpret_cast<const double2*>(f + o);
-  double v;
-  if (t == 0) v = mgo_relax(L, j, i, p[o - 1], pc.y, ps.x, pn.x, fc.x);  // (i >= 2: o - 1 is column i - 1 >= 1)
-  else v = mgo_relax(L, j, i, pc.x, p[o + 2], ps.y, pn.y, fc.y);        // (o + 2: column i + 1 <= nx + 1 < pitch)
-  p[o + t] = v;
-}
-
-// nsw (1..3) whole sweeps of level l in one launch, pin -> pout: mg_smooth_tile_kernel's
-// tile (64 rows x 128 columns of p in LDS, 64 KiB), halo scheme and ownership, with the
-// channel's cell function. Cells outside rows 0 .. ny+1 / columns 0 .. nx+1 are loaded as 0
-// and, like the ghost cells, never selected.
-__global__ __launch_bounds__(MG_TILE_THREADS) void mgo_smooth_tile_kernel(const MgoLevel* __restrict__ lv, int l,
-                                                                          const double* __restrict__ pin,
-                                                                          double* __restrict__ pout,
-                                                                          const double* __restrict__ f, int nsw) {
-  __shared__ double S[MG_TR * MG_TC];
-  const MgoLevel* L = lv + l;
-  const int nx = L->nx, ny = L->ny;
-  const int H = 2 * nsw, TW = MG_TC - 2 * H, TH = MG_TR - 2 * H;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c0 = 2 * lane;
-  const int gx = (int)blockIdx.x * TW - H + c0;  // even (or negative: outside)
-  const int gy0 = (int)blockIdx.y * TH - H;
-  const size_t P = (size_t)L->pitch;
-  const bool colin = gx >= 0 && gx <= nx + 1;  // (gx + 1 <= nx + 2 < pitch)
-  double2 fr[MG_TQ];
-#pragma unroll
-  for (int q = 0; q < MG_TQ; ++q) {
-    const int r = w + 16 * q, gy = gy0 + r;
-    double2 v = make_double2(0.0, 0.0);
-    fr[q] = v;
-    if (colin && gy >= 0 && gy <= ny + 1) {
-      v = *reinterpret_cast<const double2*>(pin + (size_t)gy * P + gx);
-      fr[q] = *reinterpret_cast<const double2*>(f + (size_t)gy * P + gx);
-    }
-    *reinterpret_cast<double2*>(&S[r * MG_TC + c0]) = v;
+struct MgChannel {
+  using Level = MgoLevel;
+  static constexpr bool has_pair = false;
+  static constexpr bool pair_loads = true;
+  static __device__ __forceinline__ bool unknown(const Level*, int, int) { return true; }
+  static __device__ __forceinline__ double relax(const Level* L, int j, int i, double pW, double pE, double pS, double pN,
+                                                 double f) {
+    return mgo_relax(L, j, i, pW, pE, pS, pN, f);
   }
-  __syncthreads();
-  for (int k = 0; k < 2 * nsw; ++k) {
-#pragma unroll
-    for (int q = 0; q < MG_TQ; ++q) {
-      const int r = w + 16 * q, gy = gy0 + r;
-      const int t = (gy + k) & 1;  // colour k & 1: the cells with i + j + colour even (gx is even)
-      const int c = c0 + t, i = gx + t;
-      if (r > k && r < MG_TR - 1 - k && c > k && c < MG_TC - 1 - k && gy >= 1 && gy <= ny && i >= 1 && i <= nx) {
-        const int o = r * MG_TC + c;
-        S[o] = mgo_relax(L, gy, i, S[o - 1], S[o + 1], S[o - MG_TC], S[o + MG_TC], t ? fr[q].y : fr[q].x);
-      }
-    }
-    __syncthreads();
+  static __device__ __forceinline__ double update(const Level* L, const double* p, int P, int j, int i, double f, bool sor) {
+    return sor ? mgo_sor(L, j, i, p[0], p[-1], p[1], p[-P], p[P], f) : mgo_relax(L, j, i, p[-1], p[1], p[-P], p[P], f);
   }
-#pragma unroll
-  for (int q = 0; q < MG_TQ; ++q) {
-    const int r = w + 16 * q, gy = gy0 + r;
-    if (r < H || r >= H + TH || c0 < H || c0 >= H + TW || gy < 1 || gy > ny) continue;  // (H, TW even: a pair is owned whole)
-    const double2 v = *reinterpret_cast<const double2*>(&S[r * MG_TC + c0]);
-    double* o = pout + (size_t)gy * P + gx;
-    if (gx >= 1 && gx + 1 <= nx) *reinterpret_cast<double2*>(o) = v;
-    else if (gx >= 1 && gx <= nx) o[0] = v.x;
-    else if (gx + 1 >= 1 && gx + 1 <= nx) o[1] = v.y;
+  template <bool Aligned>
+  static __device__ __forceinline__ double coarse_source(const Level* Lf, const double* p, const double* f, size_t P, int J,
+                                                         int I) {
+    return mgo_restrict_cell(Lf, p, f, P, J, I);
   }
-}
-
-// Residual of level l + restriction to level l + 1 by level l's kind; e_{l+1} = 0.
-// One thread per coarse cell; block: 4 coarse rows x 64 coarse columns.
-__global__ __launch_bounds__(256) void mgo_restrict_kernel(const MgoLevel* __restrict__ lv, int l,
-                                                           const double* __restrict__ p, const double* __restrict__ f,
-                                                           double* __restrict__ fc, double* __restrict__ ec) {
-  const MgoLevel* Lf = lv + l;
-  const MgoLevel* Lc = lv + l + 1;
-  const int I = 1 + blockIdx.x * 64 + (threadIdx.x & 63);
-  const int J = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (I > Lc->nx || J > Lc->ny) return;
-  const size_t oc = (size_t)J * Lc->pitch + I;
-  fc[oc] = mgo_restrict_cell(Lf, p, f, (size_t)Lf->pitch, J, I);
-  ec[oc] = 0.0;
-}
-
-// p_l += interpolant of e_{l+1}. Block: 4 rows x 128 columns, a lane one aligned pair.
-__global__ __launch_bounds__(256) void mgo_prolong_kernel(const MgoLevel* __restrict__ lv, int l, double* __restrict__ p,
-                                                          const double* __restrict__ ec) {
-  const MgoLevel* L = lv + l;
-  const MgoLevel* Lc = lv + l + 1;
-  const int nx = L->nx, ny = L->ny, kind = L->kind;
-  const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
-  const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (j > ny || gi > nx) return;
-  const size_t o = (size_t)j * L->pitch + gi;
-  const int pc = Lc->pitch;
-  if (gi >= 1 && gi + 1 <= nx) {
-    double2 v = *reinterpret_cast<const double2*>(p + o);
-    v.x += mgo_corr(Lc, kind, ec, pc, j, gi);
-    v.y += mgo_corr(Lc, kind, ec, pc, j, gi + 1);
-    *reinterpret_cast<double2*>(p + o) = v;
-  } else if (gi >= 1) {
-    p[o] += mgo_corr(Lc, kind, ec, pc, j, gi);  // (gi == nx)
-  } else {
-    p[o + 1] += mgo_corr(Lc, kind, ec, pc, j, 1);  // (gi == 0; nx >= 2)
+  static __device__ __forceinline__ double corr(const Level* L, const double* e, int pitch, int j, int i) {
+    return mgo_corr(L + 1, L->kind, e, pitch, j, i);
   }
-}
-
-// one colour of a sweep of a level held in LDS (rows of nx + 2), by the whole workgroup
-__device__ __forceinline__ void mgo_tail_half_sweep(const MgoLevel* L, double* p, const double* f, int colour, bool sor) {
-  const int nx = L->nx, ny = L->ny, pitch = nx + 2, hw = (nx + 1) >> 1;
-  for (int q = threadIdx.x; q < ny * hw; q += MG_TAIL_THREADS) {
-    const int j = 1 + q / hw;
-    const int i = 1 + ((j + 1 + colour) & 1) + 2 * (q % hw);
-    if (i > nx) continue;
-    const int o = j * pitch + i;
-    p[o] = sor ? mgo_sor(L, j, i, p[o], p[o - 1], p[o + 1], p[o - pitch], p[o + pitch], f[o])
-               : mgo_relax(L, j, i, p[o - 1], p[o + 1], p[o - pitch], p[o + pitch], f[o]);
-  }
-  __syncthreads();
-}
-
-// The sub-cycle over levels l0 .. last in one workgroup (mg_tail_kernel's scheme), each
-// transfer by its fine level's kind.
-__global__ __launch_bounds__(MG_TAIL_THREADS) void mgo_tail_kernel(const MgoLevel* __restrict__ lv, int l0, int last,
-                                                                   int nu1, int nu2, const double* __restrict__ fg,
-                                                                   double* __restrict__ eg) {
-  __shared__ double S[MG_LDS_DOUBLES];
-  const int tid = threadIdx.x;
-  // every level's correction starts from zero, ghosts included
-  for (int l = l0; l <= last; ++l) {
-    const MgoLevel* L = lv + l;
-    const int n = (L->nx + 2) * (L->ny + 2);
-    for (int q = tid; q < n; q += MG_TAIL_THREADS) S[L->lds_p + q] = 0.0;
-  }
-  {
-    const MgoLevel* L = lv + l0;
-    const int nx = L->nx;
-    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
-      const int j = 1 + q / nx, i = 1 + q % nx;
-      S[L->lds_f + j * (nx + 2) + i] = fg[(size_t)j * L->pitch + i];
-    }
-  }
-  __syncthreads();
-  for (int l = l0; l < last; ++l) {
-    const MgoLevel* L = lv + l;
-    const MgoLevel* Lc = L + 1;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
-    for (int s = 0; s < nu1; ++s) {
-      mgo_tail_half_sweep(L, p, f, 0, false);
-      mgo_tail_half_sweep(L, p, f, 1, false);
-    }
-    const int ncx = Lc->nx, pcp = ncx + 2;
-    for (int q = tid; q < ncx * Lc->ny; q += MG_TAIL_THREADS) {
-      const int J = 1 + q / ncx, I = 1 + q % ncx;
-      S[Lc->lds_f + J * pcp + I] = mgo_restrict_cell(L, p, f, (size_t)(L->nx + 2), J, I);
-    }
-    __syncthreads();
-  }
-  {
-    const MgoLevel* L = lv + last;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
-    for (int s = 0; s < L->coarse_sweeps; ++s) {
-      mgo_tail_half_sweep(L, p, f, 0, true);
-      mgo_tail_half_sweep(L, p, f, 1, true);
-    }
-  }
-  for (int l = last - 1; l >= l0; --l) {
-    const MgoLevel* L = lv + l;
-    const MgoLevel* Lc = L + 1;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
-    const double* e = S + Lc->lds_p;
-    const int nx = L->nx, pf = nx + 2, kind = L->kind;
-    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
-      const int j = 1 + q / nx, i = 1 + q % nx;
-      p[j * pf + i] += mgo_corr(Lc, kind, e, Lc->nx + 2, j, i);
-    }
-    __syncthreads();
-    for (int s = 0; s < nu2; ++s) {
-      mgo_tail_half_sweep(L, p, f, 0, false);
-      mgo_tail_half_sweep(L, p, f, 1, false);
-    }
-  }
-  {
-    const MgoLevel* L = lv + l0;
-    const int nx = L->nx;
-    for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
-      const int j = 1 + q / nx, i = 1 + q % nx;
-      eg[(size_t)j * L->pitch + i] = S[L->lds_p + j * (nx + 2) + i];
-    }
-  }
-}
+};
 
 // =============================================================== the step ==
 // The third scheme (mg.hpp "the step", tests/mg_step_reference.py): the
-// channel's streams, tile, halo and tail schemes over the fluid cells of the
-// backwards-facing step. Two integer compares tell fluid from solid; a
-// neighbour exists if it is inside the grid and fluid. The pair A = (jm+1,
-// si+1), B = (jm, si) is coupled through the eliminated corner solid and has
-// one colour: wherever a colour is updated, the thread that owns A forms both
-// new values from the values of before the phase and writes both, and the
-// thread that owns B writes nothing - no thread reads a cell another one
-// writes in the same phase.
+// channel's operator over the fluid cells of the backwards-facing step. Two
+// integer compares tell fluid from solid; a neighbour exists if it is inside
+// the grid and fluid. The pair A = (jm+1, si+1), B = (jm, si) is coupled
+// through the eliminated corner solid and has one colour ("the kernels").
 
 __device__ __forceinline__ bool mgs_fluid(const MgsLevel* L, int j, int i) { return i > L->si || j <= L->jm; }
 __device__ __forceinline__ bool mgs_is_a(const MgsLevel* L, int j, int i) { return j == L->jm + 1 && i == L->si + 1; }
@@ -752,37 +379,106 @@ __device__ __forceinline__ double mgs_corr(const MgsLevel* Lc, int kind, const d
   return (((9.0 * c + 3.0 * V) + 3.0 * H) + D) * 0.0625;
 }
 
-// One colour of a sweep of level l, in place. Block: 4 rows x 128 columns, a lane one column pair and in
-// it the colour's cell. A's thread writes A and B (both from the values of before the launch).
-__global__ __launch_bounds__(256) void mgs_smooth_kernel(const MgsLevel* __restrict__ lv, int l, double* p,
-                                                         const double* __restrict__ f, int colour) {
-  const MgsLevel* L = lv + l;
+struct MgStep {
+  using Level = MgsLevel;
+  static constexpr bool has_pair = true;     // A's thread writes A and B, B's own writes nothing
+  static constexpr bool pair_loads = false;  // the pair's diagonal neighbours: scalar loads around the cell
+  static __device__ __forceinline__ bool unknown(const Level* L, int j, int i) { return mgs_fluid(L, j, i); }
+  static __device__ __forceinline__ bool is_a(const Level* L, int j, int i) { return mgs_is_a(L, j, i); }
+  static __device__ __forceinline__ bool is_b(const Level* L, int j, int i) { return mgs_is_b(L, j, i); }
+  static __device__ __forceinline__ double update(const Level* L, const double* p, int P, int j, int i, double f, bool sor) {
+    return mgs_update(L, p, P, j, i, f, sor);
+  }
+  template <bool Aligned>
+  static __device__ __forceinline__ double coarse_source(const Level* Lf, const double* p, const double* f, size_t P, int J,
+                                                         int I) {
+    return mgs_restrict_cell(Lf, p, f, P, J, I);
+  }
+  static __device__ __forceinline__ double corr(const Level* L, const double* e, int pitch, int j, int i) {
+    return mgs_corr(L + 1, L->kind, e, pitch, j, i);
+  }
+};
+
+template <class Level> struct MgSchemeOf;
+template <> struct MgSchemeOf<MgLevel> { using type = MgCavity; };
+template <> struct MgSchemeOf<MgoLevel> { using type = MgChannel; };
+template <> struct MgSchemeOf<MgsLevel> { using type = MgStep; };
+
+// ============================================================ the kernels ==
+
+// A coupled pair A = (jm+1, si+1), B = (jm, si) has one colour: wherever a colour is updated (the colour
+// launch, the tile, the tail's half sweep), the thread that owns A forms both new values from the values of
+// before the phase and writes both, and the thread that owns B writes nothing - no thread reads a cell
+// another one writes in the same phase.
+
+// ------------------------------------------------------ multi-launch levels --
+
+// One colour of a sweep of level l, in place. Block: 4 waves = 4 rows x 128 columns, a lane the column pair
+// (gi, gi + 1) and in it the colour's cell.
+template <class S>
+__global__ __launch_bounds__(256) void mg_smooth_kernel(const typename S::Level* __restrict__ lv, int l, double* p,
+                                                        const double* __restrict__ f, int colour) {
+  const typename S::Level* L = lv + l;
   const int nx = L->nx, ny = L->ny;
-  const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
+  const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);  // even: a 16-B aligned pair
   const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j > ny || gi > nx) return;
-  const int i = gi + ((j + colour) & 1);  // colour 0 holds the cells with i + j even
-  if (i < 1 || i > nx || !mgs_fluid(L, j, i) || mgs_is_b(L, j, i)) return;
-  const int P = L->pitch;
-  const size_t o = (size_t)j * P + i;
-  const double v = mgs_update(L, p + o, P, j, i, f[o], false);
-  if (mgs_is_a(L, j, i)) {
-    const size_t ob = o - P - 1;
-    const double vb = mgs_update(L, p + ob, P, j - 1, i - 1, f[ob], false);
-    p[ob] = vb;
+  const int t = (j + colour) & 1;  // colour 0 holds the cells with i + j even: component t of the pair
+  const int i = gi + t;
+  if (i < 1 || i > nx) return;
+  if constexpr (S::pair_loads) {
+    static_assert(!S::has_pair, "the pair's diagonal neighbours are not in the aligned loads");
+    const size_t P = (size_t)L->pitch, o = (size_t)j * P + gi;
+    const double2 pc = *reinterpret_cast<const double2*>(p + o);
+    const double2 ps = *reinterpret_cast<const double2*>(p + o - P);
+    const double2 pn = *reinterpret_cast<const double2*>(p + o + P);
+    const double2 fc = *reinterpret_cast<const double2*>(f + o);
+    double v;
+    if (t == 0) v = S::relax(L, j, i, p[o - 1], pc.y, ps.x, pn.x, fc.x);  // (i >= 2: o - 1 is column i - 1 >= 1)
+    else v = S::relax(L, j, i, pc.x, p[o + 2], ps.y, pn.y, fc.y);        // (o + 2: column i + 1 <= nx + 1 < pitch)
+    p[o + t] = v;
+  } else {
+    if (!S::unknown(L, j, i)) return;
+    if constexpr (S::has_pair) {
+      if (S::is_b(L, j, i)) return;
+    }
+    const int P = L->pitch;
+    const size_t o = (size_t)j * P + i;
+    const double v = S::update(L, p + o, P, j, i, f[o], false);
+    if constexpr (S::has_pair) {
+      if (S::is_a(L, j, i)) {  // both from the values of before the launch
+        const size_t ob = o - P - 1;
+        const double vb = S::update(L, p + ob, P, j - 1, i - 1, f[ob], false);
+        p[ob] = vb;
+      }
+    }
+    p[o] = v;
   }
-  p[o] = v;
 }
 
-// nsw (1..3) whole sweeps of level l in one launch, pin -> pout: mgo_smooth_tile_kernel's tile,
-// halo scheme and ownership. Only fluid cells are updated and written. The pair is a diagonal
-// dependency (Chebyshev distance 1): the halo's shrink of one cell per phase holds for it.
-__global__ __launch_bounds__(MG_TILE_THREADS) void mgs_smooth_tile_kernel(const MgsLevel* __restrict__ lv, int l,
-                                                                          const double* __restrict__ pin,
-                                                                          double* __restrict__ pout,
-                                                                          const double* __restrict__ f, int nsw) {
-  __shared__ double S[MG_TR * MG_TC];
-  const MgsLevel* L = lv + l;
+// nsw (1..3) whole sweeps of level l in one launch, pin -> pout (as tile.hip
+// does for SOR). A workgroup of 16 waves holds a region of MG_TR rows x 128
+// columns of p in LDS: its tile plus H = 2 nsw cells of halo on every side,
+// since each colour phase leaves one more ring next to the region's border
+// stale. Phase k (colour k & 1 of sweep k >> 1) updates the cells at least
+// k + 1 from the border; after 2 nsw phases the tile itself (margin H) holds
+// what the sweeps over the whole level give - the halo cells are recomputed by
+// the neighbouring workgroups, same operands, same bits. p and f are read
+// once (1.2x with the halos) and p written once: 24-28 B per cell for nsw
+// sweeps where the colour launches move up to 48 per sweep. Lane l owns the
+// aligned column pair (2l, 2l + 1) of rows w, w + 16, ... and keeps their f
+// in registers; region column c is global column bx TW - H + c (even offset:
+// the pairs stay 16-B aligned), region row r global row by TH - H + r. Cells
+// outside rows 0 .. ny+1 / columns 0 .. nx+1 are loaded as 0. Only unknowns
+// are updated and written. A coupled pair is a diagonal dependency (Chebyshev
+// distance 1): the halo's shrink of one cell per phase holds for it.
+template <class S>
+__global__ __launch_bounds__(MG_TILE_THREADS) void mg_smooth_tile_kernel(const typename S::Level* __restrict__ lv, int l,
+                                                                         const double* __restrict__ pin,
+                                                                         double* __restrict__ pout,
+                                                                         const double* __restrict__ f, int nsw) {
+  __shared__ double T[MG_TR * MG_TC];
+  const typename S::Level* L = lv + l;
   const int nx = L->nx, ny = L->ny;
   const int H = 2 * nsw, TW = MG_TC - 2 * H, TH = MG_TR - 2 * H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -801,7 +497,7 @@ __global__ __launch_bounds__(MG_TILE_THREADS) void mgs_smooth_tile_kernel(const 
       v = *reinterpret_cast<const double2*>(pin + (size_t)gy * P + gx);
       fr[q] = *reinterpret_cast<const double2*>(f + (size_t)gy * P + gx);
     }
-    *reinterpret_cast<double2*>(&S[r * MG_TC + c0]) = v;
+    *reinterpret_cast<double2*>(&T[r * MG_TC + c0]) = v;
   }
   __syncthreads();
   for (int k = 0; k < 2 * nsw; ++k) {
@@ -810,17 +506,22 @@ __global__ __launch_bounds__(MG_TILE_THREADS) void mgs_smooth_tile_kernel(const 
       const int r = w + 16 * q, gy = gy0 + r;
       const int t = (gy + k) & 1;  // colour k & 1: the cells with i + j + colour even (gx is even)
       const int c = c0 + t, i = gx + t;
-      if (gy < 1 || gy > ny || i < 1 || i > nx || !mgs_fluid(L, gy, i) || mgs_is_b(L, gy, i)) continue;
       const int o = r * MG_TC + c;
       const bool own = r > k && r < MG_TR - 1 - k && c > k && c < MG_TC - 1 - k;
-      // B = (r - 1, c - 1) by A's thread, under B's own condition (then A, at least k from the border, holds
-      // its value of before the phase; r - 1 > k >= 0 and c - 1 > k keep the cell and its neighbours inside)
-      const bool pair = mgs_is_a(L, gy, i) && r - 1 > k && r - 1 < MG_TR - 1 - k && c - 1 > k && c - 1 < MG_TC - 1 - k;
-      double v = 0.0, vb = 0.0;
-      if (own) v = mgs_update(L, S + o, MG_TC, gy, i, t ? fr[q].y : fr[q].x, false);
-      if (pair) vb = mgs_update(L, S + o - MG_TC - 1, MG_TC, gy - 1, i - 1, f[(size_t)(gy - 1) * P + (i - 1)], false);
-      if (own) S[o] = v;
-      if (pair) S[o - MG_TC - 1] = vb;
+      const bool cell = gy >= 1 && gy <= ny && i >= 1 && i <= nx;
+      if constexpr (S::has_pair) {
+        if (!cell || !S::unknown(L, gy, i) || S::is_b(L, gy, i)) continue;
+        // B = (r - 1, c - 1) by A's thread, under B's own condition (then A, at least k from the border, holds
+        // its value of before the phase; r - 1 > k >= 0 and c - 1 > k keep the cell and its neighbours inside)
+        const bool pair = S::is_a(L, gy, i) && r - 1 > k && r - 1 < MG_TR - 1 - k && c - 1 > k && c - 1 < MG_TC - 1 - k;
+        double v = 0.0, vb = 0.0;
+        if (own) v = S::update(L, T + o, MG_TC, gy, i, t ? fr[q].y : fr[q].x, false);
+        if (pair) vb = S::update(L, T + o - MG_TC - 1, MG_TC, gy - 1, i - 1, f[(size_t)(gy - 1) * P + (i - 1)], false);
+        if (own) T[o] = v;
+        if (pair) T[o - MG_TC - 1] = vb;
+      } else {
+        if (own && cell) T[o] = S::update(L, T + o, MG_TC, gy, i, t ? fr[q].y : fr[q].x, false);
+      }
     }
     __syncthreads();
   }
@@ -828,145 +529,159 @@ __global__ __launch_bounds__(MG_TILE_THREADS) void mgs_smooth_tile_kernel(const 
   for (int q = 0; q < MG_TQ; ++q) {
     const int r = w + 16 * q, gy = gy0 + r;
     if (r < H || r >= H + TH || c0 < H || c0 >= H + TW || gy < 1 || gy > ny) continue;  // (H, TW even: a pair is owned whole)
-    const double2 v = *reinterpret_cast<const double2*>(&S[r * MG_TC + c0]);
+    const double2 v = *reinterpret_cast<const double2*>(&T[r * MG_TC + c0]);
     double* o = pout + (size_t)gy * P + gx;
-    const bool wa = gx >= 1 && gx <= nx && mgs_fluid(L, gy, gx), wb = gx + 1 >= 1 && gx + 1 <= nx && mgs_fluid(L, gy, gx + 1);
+    const bool wa = gx >= 1 && gx <= nx && S::unknown(L, gy, gx), wb = gx + 1 >= 1 && gx + 1 <= nx && S::unknown(L, gy, gx + 1);
     if (wa && wb) *reinterpret_cast<double2*>(o) = v;
     else if (wa) o[0] = v.x;
     else if (wb) o[1] = v.y;
   }
 }
 
-// Residual of level l + restriction to level l + 1 by level l's kind; e_{l+1} = 0.
-// One thread per coarse cell; block: 4 coarse rows x 64 coarse columns.
-__global__ __launch_bounds__(256) void mgs_restrict_kernel(const MgsLevel* __restrict__ lv, int l,
-                                                           const double* __restrict__ p, const double* __restrict__ f,
-                                                           double* __restrict__ fc, double* __restrict__ ec) {
-  const MgsLevel* Lf = lv + l;
-  const MgsLevel* Lc = lv + l + 1;
+// Residual of level l + restriction to level l + 1 (full weighting, or over the two children along the
+// direction level l halves); e_{l+1} = 0. One thread per coarse cell; block: 4 coarse rows x 64 coarse columns.
+template <class S>
+__global__ __launch_bounds__(256) void mg_restrict_kernel(const typename S::Level* __restrict__ lv, int l,
+                                                          const double* __restrict__ p, const double* __restrict__ f,
+                                                          double* __restrict__ fc, double* __restrict__ ec) {
+  const typename S::Level* Lf = lv + l;
+  const typename S::Level* Lc = lv + l + 1;
   const int I = 1 + blockIdx.x * 64 + (threadIdx.x & 63);
   const int J = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
   if (I > Lc->nx || J > Lc->ny) return;
   const size_t oc = (size_t)J * Lc->pitch + I;
-  fc[oc] = mgs_restrict_cell(Lf, p, f, (size_t)Lf->pitch, J, I);
+  fc[oc] = S::template coarse_source<true>(Lf, p, f, (size_t)Lf->pitch, J, I);
   ec[oc] = 0.0;
 }
 
-// p_l += interpolant of e_{l+1} on the fluid cells. Block: 4 rows x 128 columns, a lane one aligned pair.
-__global__ __launch_bounds__(256) void mgs_prolong_kernel(const MgsLevel* __restrict__ lv, int l, double* __restrict__ p,
-                                                          const double* __restrict__ ec) {
-  const MgsLevel* L = lv + l;
-  const MgsLevel* Lc = lv + l + 1;
-  const int nx = L->nx, ny = L->ny, kind = L->kind;
+// p_l += interpolant of e_{l+1} on the unknowns. Block: 4 rows x 128 columns, a lane one aligned pair.
+template <class S>
+__global__ __launch_bounds__(256) void mg_prolong_kernel(const typename S::Level* __restrict__ lv, int l,
+                                                         double* __restrict__ p, const double* __restrict__ ec) {
+  const typename S::Level* L = lv + l;
+  const int nx = L->nx, ny = L->ny;
   const int gi = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
   const int j = 1 + blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j > ny || gi > nx) return;
   const size_t o = (size_t)j * L->pitch + gi;
-  const int pc = Lc->pitch;
-  const bool wa = gi >= 1 && mgs_fluid(L, j, gi), wb = gi + 1 <= nx && mgs_fluid(L, j, gi + 1);
+  const int pc = (L + 1)->pitch;
+  const bool wa = gi >= 1 && S::unknown(L, j, gi), wb = gi + 1 <= nx && S::unknown(L, j, gi + 1);  // (nx >= 2)
   if (wa && wb) {
     double2 v = *reinterpret_cast<const double2*>(p + o);
-    v.x += mgs_corr(Lc, kind, ec, pc, j, gi);
-    v.y += mgs_corr(Lc, kind, ec, pc, j, gi + 1);
+    v.x += S::corr(L, ec, pc, j, gi);
+    v.y += S::corr(L, ec, pc, j, gi + 1);
     *reinterpret_cast<double2*>(p + o) = v;
   } else if (wa) {
-    p[o] += mgs_corr(Lc, kind, ec, pc, j, gi);
+    p[o] += S::corr(L, ec, pc, j, gi);  // (gi == nx, or its east neighbour is no unknown)
   } else if (wb) {
-    p[o + 1] += mgs_corr(Lc, kind, ec, pc, j, gi + 1);
+    p[o + 1] += S::corr(L, ec, pc, j, gi + 1);  // (gi == 0, or gi is no unknown)
   }
 }
 
+// ------------------------------------------------------- one-launch tail --
+
 // one colour of a sweep of a level held in LDS (rows of nx + 2), by the whole workgroup
-__device__ __forceinline__ void mgs_tail_half_sweep(const MgsLevel* L, double* p, const double* f, int colour, bool sor) {
+template <class S>
+__device__ __forceinline__ void mg_tail_half_sweep(const typename S::Level* L, double* p, const double* f, int colour,
+                                                   bool sor) {
   const int nx = L->nx, ny = L->ny, pitch = nx + 2, hw = (nx + 1) >> 1;
   for (int q = threadIdx.x; q < ny * hw; q += MG_TAIL_THREADS) {
     const int j = 1 + q / hw;
     const int i = 1 + ((j + 1 + colour) & 1) + 2 * (q % hw);
-    if (i > nx || !mgs_fluid(L, j, i) || mgs_is_b(L, j, i)) continue;
+    if (i > nx || !S::unknown(L, j, i)) continue;
+    if constexpr (S::has_pair) {
+      if (S::is_b(L, j, i)) continue;
+    }
     const int o = j * pitch + i;
-    const double v = mgs_update(L, p + o, pitch, j, i, f[o], sor);
-    if (mgs_is_a(L, j, i)) {
-      const int ob = o - pitch - 1;
-      const double vb = mgs_update(L, p + ob, pitch, j - 1, i - 1, f[ob], sor);
-      p[ob] = vb;
+    const double v = S::update(L, p + o, pitch, j, i, f[o], sor);
+    if constexpr (S::has_pair) {
+      if (S::is_a(L, j, i)) {
+        const int ob = o - pitch - 1;
+        const double vb = S::update(L, p + ob, pitch, j - 1, i - 1, f[ob], sor);
+        p[ob] = vb;
+      }
     }
     p[o] = v;
   }
   __syncthreads();
 }
 
-// The sub-cycle over levels l0 .. last in one workgroup (mgo_tail_kernel's scheme).
-__global__ __launch_bounds__(MG_TAIL_THREADS) void mgs_tail_kernel(const MgsLevel* __restrict__ lv, int l0, int last,
-                                                                   int nu1, int nu2, const double* __restrict__ fg,
-                                                                   double* __restrict__ eg) {
-  __shared__ double S[MG_LDS_DOUBLES];
+// The sub-cycle over levels l0 .. last in one workgroup, each transfer by its fine level.
+template <class S>
+__global__ __launch_bounds__(MG_TAIL_THREADS) void mg_tail_kernel(const typename S::Level* __restrict__ lv, int l0,
+                                                                  int last, int nu1, int nu2,
+                                                                  const double* __restrict__ fg, double* __restrict__ eg) {
+  using Level = typename S::Level;
+  __shared__ double T[MG_LDS_DOUBLES];
   const int tid = threadIdx.x;
-  // every level's correction starts from zero, ghosts and solid cells included
+  // every level's correction starts from zero, ghosts (and cells that are no unknowns) included
   for (int l = l0; l <= last; ++l) {
-    const MgsLevel* L = lv + l;
+    const Level* L = lv + l;
     const int n = (L->nx + 2) * (L->ny + 2);
-    for (int q = tid; q < n; q += MG_TAIL_THREADS) S[L->lds_p + q] = 0.0;
+    for (int q = tid; q < n; q += MG_TAIL_THREADS) T[L->lds_p + q] = 0.0;
   }
   {
-    const MgsLevel* L = lv + l0;
+    const Level* L = lv + l0;
     const int nx = L->nx;
     for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
       const int j = 1 + q / nx, i = 1 + q % nx;
-      S[L->lds_f + j * (nx + 2) + i] = fg[(size_t)j * L->pitch + i];
+      T[L->lds_f + j * (nx + 2) + i] = fg[(size_t)j * L->pitch + i];
     }
   }
   __syncthreads();
   for (int l = l0; l < last; ++l) {
-    const MgsLevel* L = lv + l;
-    const MgsLevel* Lc = L + 1;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
+    const Level* L = lv + l;
+    const Level* Lc = L + 1;
+    double* p = T + L->lds_p;
+    const double* f = T + L->lds_f;
     for (int s = 0; s < nu1; ++s) {
-      mgs_tail_half_sweep(L, p, f, 0, false);
-      mgs_tail_half_sweep(L, p, f, 1, false);
+      mg_tail_half_sweep<S>(L, p, f, 0, false);
+      mg_tail_half_sweep<S>(L, p, f, 1, false);
     }
     const int ncx = Lc->nx, pcp = ncx + 2;
     for (int q = tid; q < ncx * Lc->ny; q += MG_TAIL_THREADS) {
       const int J = 1 + q / ncx, I = 1 + q % ncx;
-      S[Lc->lds_f + J * pcp + I] = mgs_restrict_cell(L, p, f, (size_t)(L->nx + 2), J, I);
+      T[Lc->lds_f + J * pcp + I] = S::template coarse_source<false>(L, p, f, (size_t)(L->nx + 2), J, I);
     }
     __syncthreads();
   }
   {
-    const MgsLevel* L = lv + last;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
+    const Level* L = lv + last;
+    double* p = T + L->lds_p;
+    const double* f = T + L->lds_f;
     for (int s = 0; s < L->coarse_sweeps; ++s) {
-      mgs_tail_half_sweep(L, p, f, 0, true);
-      mgs_tail_half_sweep(L, p, f, 1, true);
+      mg_tail_half_sweep<S>(L, p, f, 0, true);
+      mg_tail_half_sweep<S>(L, p, f, 1, true);
     }
   }
   for (int l = last - 1; l >= l0; --l) {
-    const MgsLevel* L = lv + l;
-    const MgsLevel* Lc = L + 1;
-    double* p = S + L->lds_p;
-    const double* f = S + L->lds_f;
-    const double* e = S + Lc->lds_p;
-    const int nx = L->nx, pf = nx + 2, kind = L->kind;
+    const Level* L = lv + l;
+    double* p = T + L->lds_p;
+    const double* f = T + L->lds_f;
+    const double* e = T + (L + 1)->lds_p;
+    const int nx = L->nx, pf = nx + 2, pe = (L + 1)->nx + 2;
     for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
       const int j = 1 + q / nx, i = 1 + q % nx;
-      if (mgs_fluid(L, j, i)) p[j * pf + i] += mgs_corr(Lc, kind, e, Lc->nx + 2, j, i);
+      if (S::unknown(L, j, i)) p[j * pf + i] += S::corr(L, e, pe, j, i);
     }
     __syncthreads();
     for (int s = 0; s < nu2; ++s) {
-      mgs_tail_half_sweep(L, p, f, 0, false);
-      mgs_tail_half_sweep(L, p, f, 1, false);
+      mg_tail_half_sweep<S>(L, p, f, 0, false);
+      mg_tail_half_sweep<S>(L, p, f, 1, false);
     }
   }
   {
-    const MgsLevel* L = lv + l0;
+    const Level* L = lv + l0;
     const int nx = L->nx;
     for (int q = tid; q < nx * L->ny; q += MG_TAIL_THREADS) {
       const int j = 1 + q / nx, i = 1 + q % nx;
-      eg[(size_t)j * L->pitch + i] = S[L->lds_p + j * (nx + 2) + i];
+      eg[(size_t)j * L->pitch + i] = T[L->lds_p + j * (nx + 2) + i];
     }
   }
 }
+
+// ---------------------------------------------------------- the step only --
+
 
 // The reference's ghost and solid refresh of level 0 (mg.hpp: mgs_refresh_launch). Thread t serves row t
 // (its west and east ghosts, its face-column cell) and column t (its south and north ghosts, its face-row
@@ -1011,32 +726,52 @@ __global__ __launch_bounds__(256) void mgs_copy_back_kernel(int nx, int ny, int 
 
 }  // namespace
 
-void mgs_smooth_launch(const MgsLevel* dlv, const MgsLevel& L, int l, double* p, const double* f, int colour, void* stream) {
+template <class Level>
+void mg_smooth_launch(const Level* dlv, const Level& L, int l, double* p, const double* f, int colour, void* stream) {
   const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
-  mgs_smooth_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, colour);
+  mg_smooth_kernel<typename MgSchemeOf<Level>::type><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, colour);
 }
 
-void mgs_smooth_tile_launch(const MgsLevel* dlv, const MgsLevel& L, int l, const double* pin, double* pout,
-                            const double* f, int nsw, void* stream) {
+template <class Level>
+void mg_smooth_tile_launch(const Level* dlv, const Level& L, int l, const double* pin, double* pout, const double* f,
+                           int nsw, void* stream) {
   const int H = 2 * nsw;
   const dim3 grid(L.nx / (MG_TC - 2 * H) + 1, L.ny / (MG_TR - 2 * H) + 1);
-  mgs_smooth_tile_kernel<<<grid, MG_TILE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, pin, pout, f, nsw);
+  mg_smooth_tile_kernel<typename MgSchemeOf<Level>::type>
+      <<<grid, MG_TILE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, pin, pout, f, nsw);
 }
 
-void mgs_restrict_launch(const MgsLevel* dlv, const MgsLevel& Lc, int l, const double* p,
-                         const double* f, double* fc, double* ec, void* stream) {
+template <class Level>
+void mg_restrict_launch(const Level* dlv, const Level& Lc, int l, const double* p, const double* f, double* fc,
+                        double* ec, void* stream) {
   const dim3 grid((Lc.nx + 63) / 64, (Lc.ny + 3) / 4);
-  mgs_restrict_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, fc, ec);
+  mg_restrict_kernel<typename MgSchemeOf<Level>::type><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, fc, ec);
 }
 
-void mgs_prolong_launch(const MgsLevel* dlv, const MgsLevel& L, int l, double* p, const double* ec, void* stream) {
+template <class Level>
+void mg_prolong_launch(const Level* dlv, const Level& L, int l, double* p, const double* ec, void* stream) {
   const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
-  mgs_prolong_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, ec);
+  mg_prolong_kernel<typename MgSchemeOf<Level>::type><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, ec);
 }
 
-void mgs_tail_launch(const MgsLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream) {
-  mgs_tail_kernel<<<1, MG_TAIL_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l0, last, nu1, nu2, fg, eg);
+template <class Level>
+void mg_tail_launch(const Level* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream) {
+  mg_tail_kernel<typename MgSchemeOf<Level>::type>
+      <<<1, MG_TAIL_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l0, last, nu1, nu2, fg, eg);
 }
+
+#define MG_INSTANTIATE(Level)                                                                                              \
+  template void mg_smooth_launch<Level>(const Level*, const Level&, int, double*, const double*, int, void*);              \
+  template void mg_smooth_tile_launch<Level>(const Level*, const Level&, int, const double*, double*, const double*, int,  \
+                                             void*);                                                                       \
+  template void mg_restrict_launch<Level>(const Level*, const Level&, int, const double*, const double*, double*, double*, \
+                                          void*);                                                                          \
+  template void mg_prolong_launch<Level>(const Level*, const Level&, int, double*, const double*, void*);                  \
+  template void mg_tail_launch<Level>(const Level*, int, int, int, int, const double*, double*, void*);
+MG_INSTANTIATE(MgLevel)
+MG_INSTANTIATE(MgoLevel)
+MG_INSTANTIATE(MgsLevel)
+#undef MG_INSTANTIATE
 
 void mgs_refresh_launch(const MgsLevel& L, double* cur, const double* prev, const double* own, void* stream) {
   const int n = std::max(L.nx, L.ny) + 1;
@@ -1049,58 +784,5 @@ void mgs_copy_back_launch(const MgsLevel& L, double* dst, const double* src, voi
   mgs_copy_back_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(L.nx, L.ny, L.pitch, L.si, L.jm, dst, src);
 }
 
-void mgo_smooth_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* f, int colour, void* stream) {
-  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
-  mgo_smooth_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, colour);
-}
-
-void mgo_smooth_tile_launch(const MgoLevel* dlv, const MgoLevel& L, int l, const double* pin, double* pout,
-                            const double* f, int nsw, void* stream) {
-  const int H = 2 * nsw;
-  const dim3 grid(L.nx / (MG_TC - 2 * H) + 1, L.ny / (MG_TR - 2 * H) + 1);
-  mgo_smooth_tile_kernel<<<grid, MG_TILE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, pin, pout, f, nsw);
-}
-
-void mgo_restrict_launch(const MgoLevel* dlv, const MgoLevel& Lc, int l, const double* p,
-                         const double* f, double* fc, double* ec, void* stream) {
-  const dim3 grid((Lc.nx + 63) / 64, (Lc.ny + 3) / 4);
-  mgo_restrict_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, fc, ec);
-}
-
-void mgo_prolong_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* ec, void* stream) {
-  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
-  mgo_prolong_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, ec);
-}
-
-void mgo_tail_launch(const MgoLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream) {
-  mgo_tail_kernel<<<1, MG_TAIL_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l0, last, nu1, nu2, fg, eg);
-}
-
-void mg_smooth_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* f, int colour, void* stream) {
-  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
-  mg_smooth_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, colour);
-}
-
-void mg_smooth_tile_launch(const MgLevel* dlv, const MgLevel& L, int l, const double* pin, double* pout, const double* f,
-                           int nsw, void* stream) {
-  const int H = 2 * nsw;
-  const dim3 grid(L.nx / (MG_TC - 2 * H) + 1, L.ny / (MG_TR - 2 * H) + 1);
-  mg_smooth_tile_kernel<<<grid, MG_TILE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, pin, pout, f, nsw);
-}
-
-void mg_restrict_launch(const MgLevel* dlv, const MgLevel& Lc, int l, const double* p, const double* f, double* fc,
-                        double* ec, void* stream) {
-  const dim3 grid((Lc.nx + 63) / 64, (Lc.ny + 3) / 4);
-  mg_restrict_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, f, fc, ec);
-}
-
-void mg_prolong_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* ec, void* stream) {
-  const dim3 grid(L.nx / 128 + 1, (L.ny + 3) / 4);
-  mg_prolong_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(dlv, l, p, ec);
-}
-
-void mg_tail_launch(const MgLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream) {
-  mg_tail_kernel<<<1, MG_TAIL_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dlv, l0, last, nu1, nu2, fg, eg);
-}
 
 }  // namespace cfd

@@ -1,22 +1,18 @@
-// mg.hpp — geometric multigrid for the cavity-like pressure equation (the
-// cavity and Rayleigh-Benard): the plan (host only, params.cpp)
-// and the launches of mg.hip. No HIP types here, so host-only code may
-// include it (streams travel as void*, like comm.hip's).
+// mg.hpp — geometric multigrid for the pressure equation: the
+// plans (host only, params.cpp) and the launches of mg.hip. No HIP types here,
+// so host-only code may include it (streams travel as void*, like comm.hip's).
 //
-// The operator is the reference's (cavity-01.cpp:643-677): Neumann west, east
-// and north, and a Dirichlet zero in the bottom ghost row (eps_s = j_min = 1
-// and the ghost row of the fresh pressure field stays 0), i.e. p = 0 at
-// y = -h/2. Level l (spacing 2^l h) keeps that zero where the finest grid has
-// it: its row 1 sees it d_l = 0.5 + 0.5^(l+1) spacings away, so the south
-// coefficient of row 1 is cS_l = 1/d_l. A coarse level that moved the zero to
-// its own ghost centre (-H/2) makes the cycle diverge.
-//
-// A V(nu1, nu2) cycle: red-black Gauss-Seidel sweeps, residual + full-weighting
-// restriction (the residual never reaches memory), the coarsest level by a
-// fixed number of SOR sweeps in one workgroup, bilinear prolongation added to
-// p. Every constant is formed on the host; the kernels add, subtract and
-// multiply in the order tests/mg_reference.py states, so cycle counts,
-// residuals and p are that restatement's, bit for bit.
+// One set of kernels and one cycle serve three schemes, each an operator with
+// its level type and its plan:
+//   the cavity and Rayleigh-Benard (CFD_POISSON_MULTIGRID, MgLevel),
+//   the channel (CFD_POISSON_MULTIGRID_OPEN, MgoLevel),
+//   the backwards-facing step (CFD_POISSON_MULTIGRID_STEP, MgsLevel).
+// A V(nu1, nu2) cycle: red-black Gauss-Seidel sweeps, residual + restriction
+// (the residual never reaches memory), the coarsest level by a fixed number of
+// SOR sweeps in one workgroup, the prolongation added to p. Every constant is
+// formed on the host; the kernels add, subtract and multiply in the order the
+// scheme's numpy restatement under tests/ states, so cycle counts, residuals
+// and p are that restatement's, bit for bit.
 #pragma once
 
 #include <string>
@@ -30,136 +26,114 @@ constexpr int MG_COARSE_CELLS = 4096;   // the coarsest level holds at most this
 constexpr int MG_LDS_DOUBLES = 18432;   // 144 KiB: p and f of every level of the one-launch tail
 constexpr int MG_TAIL_THREADS = 1024;
 
-struct MgLevel {
+// What every scheme's level holds.
+struct MgLevelBase {
   int nx, ny;        // interior cells
   int pitch;         // global memory: cell (j, i) at j * pitch + i, rows 0 .. ny+1 (128-B aligned rows)
   int lds_p, lds_f;  // one-launch tail: offsets (doubles) of p and f in LDS, rows of nx + 2 (-1: not in the tail)
   int coarse_sweeps; // 4 max(nx, ny): SOR sweeps when this level is the coarsest
-  double h2, ih2;    // 4^l (dx dx) and its reciprocal
-  double cS, g;      // south coefficient of row 1 (1 / d_l); ghost factor 1 - 1 / d_l of the prolongation
-  double rdiag[16];  // 1 / (ew + ee + en + cs), index ew | ee << 1 | en << 2 | (row 1) << 3
+  double g;          // ghost factor 1 - 1 / d of the prolongation, towards the Dirichlet side
+  double rdiag[16];  // 1 / (the diagonal), indexed by the scheme's mask of a cell's neighbours
   double one_m_omega;  // coarsest SOR: 1 - omega_c, omega_c = 2 / (1 + sin(pi / (max(nx, ny) + 1)))
   double omr[16];      // omega_c * rdiag
 };
 
-struct MgPlan {
+// The cavity's operator is the reference's (cavity-01.cpp:643-677): Neumann
+// west, east and north, and a Dirichlet zero in the bottom ghost row (eps_s =
+// j_min = 1 and the ghost row of the fresh pressure field stays 0), i.e. p = 0
+// at y = -h/2. Level l (spacing 2^l h) keeps that zero where the finest grid
+// has it: its row 1 sees it d_l = 0.5 + 0.5^(l+1) spacings away, so the south
+// coefficient of row 1 is cS_l = 1/d_l. A coarse level that moved the zero to
+// its own ghost centre (-H/2) makes the cycle diverge. rdiag = 1 / (ew + ee +
+// en + cs), index ew | ee << 1 | en << 2 | (row 1) << 3; g is the south ghost's.
+// tests/mg_reference.py states every operation.
+struct MgLevel : MgLevelBase {
+  double h2, ih2;    // 4^l (dx dx) and its reciprocal
+  double cS;         // south coefficient of row 1 (1 / d_l)
+};
+
+// The channel (DESIGN.md §8 "The channel"): dx != dy, Neumann west / south /
+// north and a Dirichlet zero in the east ghost column (channel-01.cpp:642-688).
+// Level l has spacings 2^a dx and 2^b dy, cx = 1 / hx^2, cy = 1 / hy^2; column
+// nx sees the zero d = 0.5 + 0.5^(a+1) spacings away: east coefficient cE =
+// cx / d with neighbour value 0. Levels are semi-coarsened: with r = (hy /
+// hx)^2, r > 2 halves x only, r < 1/2 y only, otherwise both. Absent
+// neighbours are skipped by selects, so no ghost cell's value reaches a result.
+// rdiag = 1 / ((cw + ce) + (cs + cn)), index w | e << 1 | s << 2 | n << 3 (a
+// set bit: that neighbour exists); g is the east ghost's.
+// tests/mg_open_reference.py states every operation.
+enum { MGO_FULL = 0, MGO_X = 1, MGO_Y = 2 };
+
+// (A base of its own, ahead of the shared one: with the coefficients in the head of a level, as before the
+// three level types shared a base, the tail kernel keeps its register count - profiles/mg/refactor_resources.txt.)
+struct MgoCoef {
+  double cx, cy;     // 1 / hx^2, 1 / hy^2
+  double cE;         // east coefficient of column nx (cx / d)
+};
+
+struct MgoLevel : MgoCoef, MgLevelBase {
+  int kind;          // how this level is coarsened to the next: MGO_FULL / MGO_X / MGO_Y (-1: the coarsest)
+  int a, b;          // halvings of x and y down to this level
+};
+
+// The step: the channel's operator and semi-coarsening on the
+// backwards-facing step's fluid cells (backwards_step-01.cpp:872-939 on the
+// ghosts and solids 685-740 refresh). Level l has si = step_i >> a, jm =
+// inlet_jmax >> b; cell (J, I) is fluid iff I > si or J <= jm, and a neighbour
+// exists only inside the grid and fluid. Solid cells are no unknowns: never
+// written, never read into a result. The reference's corner solid (jm+1, si) =
+// (p_A + p_B) / 2 couples its east fluid cell A = (jm+1, si+1) and its south
+// fluid cell B = (jm, si): eliminated, A's west term is (cx/2)(p_B - p_A) and
+// B's north term (cy/2)(p_A - p_B), on every level. A and B have one colour;
+// both updates of a phase use the pre-phase values: A's thread forms both and
+// writes both, B's own skips. tests/mg_step_reference.py states every operation.
+struct MgsLevel : MgoLevel {
+  int si, jm;        // the block: solid iff i <= si and j > jm
+  double chx, chy;   // cx / 2, cy / 2: A's west and B's north coefficient
+  double rdA, rdB;   // rdiag for A (cw = chx) and B (cn = chy)
+  double omrA, omrB; // omega_c * rdA, omega_c * rdB
+};
+
+template <class Level>
+struct MgPlanOf {
   int levels = 0;
   int tail = 0;  // levels tail .. levels-1 run as one launch (tail >= 1)
-  MgLevel lv[MG_MAX_LEVELS];
+  Level lv[MG_MAX_LEVELS];
 };
+using MgPlan = MgPlanOf<MgLevel>;
+using MgoPlan = MgPlanOf<MgoLevel>;
+using MgsPlan = MgPlanOf<MgsLevel>;
 
 // The plan of a parameter block, or false with the rule that refused it in
 // `why` (host only: params.cpp).
 bool mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why);
-
-// Launches (mg.hip). dlv: the plan's levels in device memory; L: the host copy.
-// One colour of a red-black Gauss-Seidel sweep of level l, in place.
-void mg_smooth_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* f, int colour, void* stream);
-// nsw (1..3) whole sweeps of level l in one launch on LDS tiles, pin -> pout (both with zero ghost cells).
-void mg_smooth_tile_launch(const MgLevel* dlv, const MgLevel& L, int l, const double* pin, double* pout, const double* f,
-                           int nsw, void* stream);
-// f_{l+1} = -1/4 sum of the residual over each coarse cell's four children; e_{l+1} = 0.
-void mg_restrict_launch(const MgLevel* dlv, const MgLevel& Lc, int l, const double* p, const double* f, double* fc,
-                        double* ec, void* stream);
-// p_l += bilinear interpolant of e_{l+1} (its ghost layer formed on the fly).
-void mg_prolong_launch(const MgLevel* dlv, const MgLevel& L, int l, double* p, const double* ec, void* stream);
-// The sub-cycle over levels l0 .. last in one workgroup, p and f of every level in LDS:
-// f_{l0} read from fg, the correction e_{l0} written to eg.
-void mg_tail_launch(const MgLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
-
-// ------------------------------------------------------------- the channel --
-// The second scheme (CFD_POISSON_MULTIGRID_OPEN, DESIGN.md §8 "The channel"):
-// dx != dy, Neumann west / south / north and a Dirichlet zero in the east ghost
-// column (channel-01.cpp:642-688). Level l has spacings 2^a dx and 2^b dy, cx =
-// 1 / hx^2, cy = 1 / hy^2; column nx sees the zero d = 0.5 + 0.5^(a+1) spacings
-// away: east coefficient cE = cx / d with neighbour value 0. Levels are
-// semi-coarsened: with r = (hy / hx)^2, r > 2 halves x only, r < 1/2 y only,
-// otherwise both. Absent neighbours are skipped by selects, so no ghost cell's
-// value reaches a result. tests/mg_open_reference.py states every operation.
-enum { MGO_FULL = 0, MGO_X = 1, MGO_Y = 2 };
-
-struct MgoLevel {
-  int nx, ny;        // interior cells
-  int pitch;         // global memory: cell (j, i) at j * pitch + i (128-B aligned rows)
-  int lds_p, lds_f;  // one-launch tail: offsets (doubles) of p and f in LDS, rows of nx + 2 (-1: not in the tail)
-  int coarse_sweeps; // 4 max(nx, ny): SOR sweeps when this level is the coarsest
-  int kind;          // how this level is coarsened to the next: MGO_FULL / MGO_X / MGO_Y (-1: the coarsest)
-  int a, b;          // halvings of x and y down to this level
-  double cx, cy;     // 1 / hx^2, 1 / hy^2
-  double cE, g;      // east coefficient of column nx (cx / d); east ghost factor 1 - 1 / d of the prolongation
-  double rdiag[16];  // 1 / ((cw + ce) + (cs + cn)), index w | e << 1 | s << 2 | n << 3 (a set bit: that neighbour exists)
-  double one_m_omega;  // coarsest SOR: 1 - omega_c, omega_c = 2 / (1 + sin(pi / (max(nx, ny) + 1)))
-  double omr[16];      // omega_c * rdiag
-};
-
-struct MgoPlan {
-  int levels = 0;
-  int tail = 0;  // levels tail .. levels-1 run as one launch (tail >= 1)
-  MgoLevel lv[MG_MAX_LEVELS];
-};
-
-// The channel's plan of a parameter block, or false with the rule that refused it in `why` (host only: params.cpp).
 bool mgo_make_plan(const cfd_params& p, MgoPlan& plan, std::string& why);
-
-// Launches (mg.hip), as the cavity scheme's. The transfers read the kind from level l.
-void mgo_smooth_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* f, int colour, void* stream);
-void mgo_smooth_tile_launch(const MgoLevel* dlv, const MgoLevel& L, int l, const double* pin, double* pout,
-                            const double* f, int nsw, void* stream);
-void mgo_restrict_launch(const MgoLevel* dlv, const MgoLevel& Lc, int l, const double* p,
-                         const double* f, double* fc, double* ec, void* stream);
-void mgo_prolong_launch(const MgoLevel* dlv, const MgoLevel& L, int l, double* p, const double* ec, void* stream);
-void mgo_tail_launch(const MgoLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
-
-// ---------------------------------------------------------------- the step --
-// The third scheme (CFD_POISSON_MULTIGRID_STEP): the channel's
-// operator and semi-coarsening on the backwards-facing step's fluid cells
-// (backwards_step-01.cpp:872-939 on the ghosts and solids 685-740 refresh).
-// Level l has si = step_i >> a, jm = inlet_jmax >> b; cell (J, I) is fluid iff
-// I > si or J <= jm, and a neighbour exists only inside the grid and fluid.
-// Solid cells are no unknowns: never written, never read into a result. The
-// reference's corner solid (jm+1, si) = (p_A + p_B) / 2 couples its east fluid
-// cell A = (jm+1, si+1) and its south fluid cell B = (jm, si): eliminated, A's
-// west term is (cx/2)(p_B - p_A) and B's north term (cy/2)(p_A - p_B), on
-// every level. A and B have one colour; both updates of a phase use the
-// pre-phase values: A's thread forms both and writes both, B's own skips.
-// tests/mg_step_reference.py states every operation.
-struct MgsLevel {
-  int nx, ny;        // interior cells
-  int pitch;         // global memory: cell (j, i) at j * pitch + i (128-B aligned rows)
-  int lds_p, lds_f;  // one-launch tail: offsets (doubles) of p and f in LDS, rows of nx + 2 (-1: not in the tail)
-  int coarse_sweeps; // 4 max(nx, ny): SOR sweeps when this level is the coarsest
-  int kind;          // how this level is coarsened to the next: MGO_FULL / MGO_X / MGO_Y (-1: the coarsest)
-  int a, b;          // halvings of x and y down to this level
-  int si, jm;        // the block: solid iff i <= si and j > jm
-  double cx, cy;     // 1 / hx^2, 1 / hy^2
-  double chx, chy;   // cx / 2, cy / 2: A's west and B's north coefficient
-  double cE, g;      // east coefficient of column nx (cx / d); east ghost factor 1 - 1 / d of the prolongation
-  double rdiag[16];  // 1 / ((cw + ce) + (cs + cn)), index w | e << 1 | s << 2 | n << 3 (a set bit: that neighbour exists)
-  double rdA, rdB;   // the same for A (cw = chx) and B (cn = chy)
-  double one_m_omega;  // coarsest SOR: 1 - omega_c, omega_c = 2 / (1 + sin(pi / (max(nx, ny) + 1)))
-  double omr[16];      // omega_c * rdiag
-  double omrA, omrB;
-};
-
-struct MgsPlan {
-  int levels = 0;
-  int tail = 0;  // levels tail .. levels-1 run as one launch (tail >= 1)
-  MgsLevel lv[MG_MAX_LEVELS];
-};
-
-// The step's plan of a parameter block, or false with the rule that refused it in `why` (host only: params.cpp).
 bool mgs_make_plan(const cfd_params& p, MgsPlan& plan, std::string& why);
 
-// Launches (mg.hip), as the channel scheme's.
-void mgs_smooth_launch(const MgsLevel* dlv, const MgsLevel& L, int l, double* p, const double* f, int colour, void* stream);
-void mgs_smooth_tile_launch(const MgsLevel* dlv, const MgsLevel& L, int l, const double* pin, double* pout,
-                            const double* f, int nsw, void* stream);
-void mgs_restrict_launch(const MgsLevel* dlv, const MgsLevel& Lc, int l, const double* p,
-                         const double* f, double* fc, double* ec, void* stream);
-void mgs_prolong_launch(const MgsLevel* dlv, const MgsLevel& L, int l, double* p, const double* ec, void* stream);
-void mgs_tail_launch(const MgsLevel* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
-// The reference's refresh (backwards_step-01.cpp:685-740) of level 0's field `cur` (row 0 of a buffer
-// with L's pitch): the four ghost sides, the block's face row (0 + south), corner (((0 + east) +
+// Launches (mg.hip), instantiated for the three level types. dlv: the plan's
+// levels in device memory; L: the host copy of the level that sizes the grid.
+// One colour of a red-black Gauss-Seidel sweep of level l, in place.
+template <class Level>
+void mg_smooth_launch(const Level* dlv, const Level& L, int l, double* p, const double* f, int colour, void* stream);
+// nsw (1..3) whole sweeps of level l in one launch on LDS tiles, pin -> pout (both with zero ghost cells).
+template <class Level>
+void mg_smooth_tile_launch(const Level* dlv, const Level& L, int l, const double* pin, double* pout, const double* f,
+                           int nsw, void* stream);
+// f_{l+1} = minus the mean of the residual over each coarse cell's children (four, or two along the one
+// direction level l halves); e_{l+1} = 0.
+template <class Level>
+void mg_restrict_launch(const Level* dlv, const Level& Lc, int l, const double* p, const double* f, double* fc,
+                        double* ec, void* stream);
+// p_l += the interpolant of e_{l+1} (its ghost layer formed on the fly).
+template <class Level>
+void mg_prolong_launch(const Level* dlv, const Level& L, int l, double* p, const double* ec, void* stream);
+// The sub-cycle over levels l0 .. last in one workgroup, p and f of every level in LDS:
+// f_{l0} read from fg, the correction e_{l0} written to eg.
+template <class Level>
+void mg_tail_launch(const Level* dlv, int l0, int last, int nu1, int nu2, const double* fg, double* eg, void* stream);
+
+// The step only. The reference's refresh (backwards_step-01.cpp:685-740) of level 0's field `cur` (row 0
+// of a buffer with L's pitch): the four ghost sides, the block's face row (0 + south), corner (((0 + east) +
 // south) / 2) and face column (0 + east). Ghosts that copy a solid cell take an interior solid from
 // `own` (the solver's p: the only buffer that holds them) and a face cell's value of before this
 // refresh from `prev` (the buffer the previous refresh worked on).

@@ -208,60 +208,41 @@ int cfd::lexw_auto_sweeps(const cfd_params& p) {
 }
 
 // ------------------------------------------------------------ multigrid --
-// The plan of the multigrid pressure solve (mg.hpp): level 0 is
-// the solver's grid; level l+1 (half the cells per direction) exists while
-// both sizes of level l are even and the smaller is at least 8. Valid with at
-// least two levels and a coarsest level of at most MG_COARSE_CELLS cells.
-// Every constant the kernels multiply with is formed here, in the operations
-// tests/mg_reference.py states.
-bool cfd::mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why) {
-  if (p.case_id != CFD_CAVITY && p.case_id != CFD_RAYLEIGH_BENARD) {
-    why = "multigrid covers the cavity and Rayleigh-Benard (case rule): the channel has CFD_POISSON_MULTIGRID_OPEN, "
-          "the step CFD_POISSON_MULTIGRID_STEP";
-    return false;
-  }
-  if (p.nx < 2 || p.ny < 2 || !(p.dx > 0)) {
-    why = "multigrid needs a grid of at least 2 x 2 cells and dx > 0 (grid rule)";
-    return false;
-  }
-  int nx = p.nx, ny = p.ny, n = 0;
-  plan = MgPlan{};
-  for (;;) {
-    MgLevel& L = plan.lv[n];
-    L.nx = nx;
-    L.ny = ny;
-    L.pitch = ((nx + 3) + 15) / 16 * 16;  // the solver's own row pitch rule (level 0: its p and f buffers)
-    L.lds_p = L.lds_f = -1;
-    const int m = std::max(nx, ny);
-    L.coarse_sweeps = 4 * m;
-    L.h2 = std::ldexp(1.0, 2 * n) * (p.dx * p.dx);
-    L.ih2 = 1.0 / L.h2;
-    const double d = 0.5 + std::ldexp(1.0, -(n + 1));
-    L.cS = 1.0 / d;
-    L.g = 1.0 - L.cS;
-    const double pi = 3.14159265358979323846;
-    const double omega = 2.0 / (1.0 + std::sin(pi / (m + 1)));
-    L.one_m_omega = 1.0 - omega;
-    for (int k = 0; k < 16; ++k) {
-      const double ew = k & 1, ee = (k >> 1) & 1, en = (k >> 2) & 1, cs = (k & 8) ? L.cS : 1.0;
-      L.rdiag[k] = 1.0 / (((ew + ee) + en) + cs);
-      L.omr[k] = omega * L.rdiag[k];
-    }
-    ++n;
-    if (!(nx % 2 == 0 && ny % 2 == 0 && std::min(nx, ny) >= 8) || n == MG_MAX_LEVELS) break;
-    nx /= 2;
-    ny /= 2;
-  }
+// The plans of the multigrid pressure solve (mg.hpp). Every
+// constant the kernels multiply with is formed here, in the operations the
+// scheme's restatement under tests/ states.
+namespace {
+
+using namespace cfd;
+
+// What every level holds whatever its operator; returns omega_c.
+double mg_level_base(MgLevelBase& L, int nx, int ny) {
+  L.nx = nx;
+  L.ny = ny;
+  L.pitch = ((nx + 3) + 15) / 16 * 16;  // the solver's own row pitch rule (level 0: its p and f buffers)
+  L.lds_p = L.lds_f = -1;
+  const int m = std::max(nx, ny);
+  L.coarse_sweeps = 4 * m;
+  const double pi = 3.14159265358979323846;
+  const double omega = 2.0 / (1.0 + std::sin(pi / (m + 1)));
+  L.one_m_omega = 1.0 - omega;
+  return omega;
+}
+
+// The end of every plan builder, n levels made: valid with at least two levels and a coarsest level of at
+// most MG_COARSE_CELLS cells; then the one-launch tail. `head` opens the refusals ("grid ... has no ...
+// plan (grid rule): "), `second_level_rule` says what a second level needs.
+template <class Level>
+bool mg_finish_plan(MgPlanOf<Level>& plan, int n, const std::string& head, const char* second_level_rule, std::string& why) {
   plan.levels = n;
-  const MgLevel& C = plan.lv[n - 1];
+  const Level& C = plan.lv[n - 1];
   if (n < 2) {
-    why = "grid " + std::to_string(p.nx) + " x " + std::to_string(p.ny) +
-          " has no multigrid plan (grid rule): a second level needs both sizes even and at least 8";
+    why = head + second_level_rule;
     return false;
   }
   if ((long long)C.nx * C.ny > MG_COARSE_CELLS) {
-    why = "grid " + std::to_string(p.nx) + " x " + std::to_string(p.ny) + " has no multigrid plan (grid rule): its coarsest level " +
-          std::to_string(C.nx) + " x " + std::to_string(C.ny) + " holds more than " + std::to_string(MG_COARSE_CELLS) + " cells";
+    why = head + "its coarsest level " + std::to_string(C.nx) + " x " + std::to_string(C.ny) + " holds more than " +
+          std::to_string(MG_COARSE_CELLS) + " cells";
     return false;
   }
   // the one-launch tail: from the first level (>= 1) of at most MG_COARSE_CELLS
@@ -284,6 +265,152 @@ bool cfd::mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why) {
   return true;
 }
 
+// The levels of the two semi-coarsened schemes: level 0 is the solver's grid with hx = dx, hy = dy. With
+// r = (hy / hx)^2 the next level halves x only (r > 2), y only (r < 1/2) or both; a direction can be halved
+// while its size is even and at least 8 and the block allows it, and a level whose chosen direction(s)
+// cannot be halved is the coarsest. Valid with 2 .. MG_MAX_LEVELS levels. `block` is the step's geometry
+// (MgNoBlock for the channel): it fills its own fields of a level, may forbid a halving, and is halved along.
+template <class Level, class Block>
+bool mg_semi_plan(const cfd_params& p, MgPlanOf<Level>& plan, Block block, const std::string& head,
+                  const char* second_level_rule, std::string& why) {
+  int nx = p.nx, ny = p.ny, a = 0, b = 0, n = 0;
+  plan = MgPlanOf<Level>{};
+  for (;;) {
+    if (n == MG_MAX_LEVELS) {
+      why = head + "more than " + std::to_string(MG_MAX_LEVELS) + " levels";
+      return false;
+    }
+    Level& L = plan.lv[n];
+    const double omega = mg_level_base(L, nx, ny);
+    L.a = a;
+    L.b = b;
+    const double hx = std::ldexp(p.dx, a), hy = std::ldexp(p.dy, b);
+    L.cx = 1.0 / (hx * hx);
+    L.cy = 1.0 / (hy * hy);
+    const double d = 0.5 + std::ldexp(1.0, -(a + 1));
+    L.cE = L.cx / d;
+    L.g = 1.0 - 1.0 / d;
+    for (int k = 0; k < 16; ++k) {
+      const double cw = (k & 1) ? L.cx : 0.0, ce = (k & 2) ? L.cx : L.cE;
+      const double cs = (k & 4) ? L.cy : 0.0, cn = (k & 8) ? L.cy : 0.0;
+      L.rdiag[k] = 1.0 / ((cw + ce) + (cs + cn));
+      L.omr[k] = omega * L.rdiag[k];
+    }
+    block.fill(L, omega);
+    ++n;
+    const double q = hy / hx, r = q * q;
+    const bool can_x = nx % 2 == 0 && nx >= 8 && block.can_x(), can_y = ny % 2 == 0 && ny >= 8 && block.can_y(ny);
+    L.kind = -1;
+    if (r > 2.0) {
+      if (can_x) L.kind = MGO_X;
+    } else if (r < 0.5) {
+      if (can_y) L.kind = MGO_Y;
+    } else if (can_x && can_y) {
+      L.kind = MGO_FULL;
+    }
+    if (L.kind < 0) break;
+    if (L.kind != MGO_Y) nx /= 2, ++a, block.halve_x();
+    if (L.kind != MGO_X) ny /= 2, ++b, block.halve_y();
+  }
+  return mg_finish_plan(plan, n, head, second_level_rule, why);
+}
+
+struct MgNoBlock {
+  void fill(MgoLevel&, double) const {}
+  bool can_x() const { return true; }
+  bool can_y(int) const { return true; }
+  void halve_x() {}
+  void halve_y() {}
+};
+
+// The step's block, halved with the grid: si = step_i >> a and jm = inlet_jmax >> b. x can be halved while
+// si is even and at least 2; y while jm is even and at least 2 and the block is at least 2 rows high - so
+// a coarse cell's children are all fluid or all solid and every level keeps the pair A = (jm+1, si+1),
+// B = (jm, si).
+struct MgStepBlock {
+  int si, jm;
+  void fill(MgsLevel& L, double omega) const {
+    const int nx = L.nx, ny = L.ny;
+    L.si = si;
+    L.jm = jm;
+    L.chx = L.cx * 0.5;
+    L.chy = L.cy * 0.5;
+    // A = (jm+1, si+1): west through the corner (cx / 2), south fluid; B = (jm, si): north through it (cy / 2), east fluid
+    const double ceA = si + 1 < nx ? L.cx : L.cE, cnA = jm + 1 < ny ? L.cy : 0.0;
+    L.rdA = 1.0 / ((L.chx + ceA) + (L.cy + cnA));
+    const double cwB = si > 1 ? L.cx : 0.0, ceB = si < nx ? L.cx : L.cE, csB = jm > 1 ? L.cy : 0.0;
+    L.rdB = 1.0 / ((cwB + ceB) + (csB + L.chy));
+    L.omrA = omega * L.rdA;
+    L.omrB = omega * L.rdB;
+  }
+  bool can_x() const { return si % 2 == 0 && si >= 2; }
+  bool can_y(int ny) const { return jm % 2 == 0 && jm >= 2 && ny - jm >= 2; }
+  void halve_x() { si /= 2; }
+  void halve_y() { jm /= 2; }
+};
+
+std::string mg_grid_name(const cfd_params& p) { return "grid " + std::to_string(p.nx) + " x " + std::to_string(p.ny); }
+
+// cfd_mg_open_plan and cfd_mg_step_plan: the sizes of every level
+template <class Plan>
+int mg_report_levels(const cfd_params* p, bool (*make)(const cfd_params&, Plan&, std::string&), int* levels, int* level_nx,
+                     int* level_ny) {
+  if (!p) {
+    set_last_error("null params");
+    return CFD_E_ARG;
+  }
+  Plan plan;
+  std::string why;
+  if (!make(*p, plan, why)) {
+    set_last_error(why);
+    return CFD_E_ARG;
+  }
+  if (levels) *levels = plan.levels;
+  for (int l = 0; l < MG_MAX_LEVELS; ++l) {
+    if (level_nx) level_nx[l] = l < plan.levels ? plan.lv[l].nx : 0;
+    if (level_ny) level_ny[l] = l < plan.levels ? plan.lv[l].ny : 0;
+  }
+  return CFD_OK;
+}
+
+}  // namespace
+
+// The cavity's plan: level l+1 (half the cells per direction) exists while both
+// sizes of level l are even and the smaller is at least 8.
+bool cfd::mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why) {
+  if (p.case_id != CFD_CAVITY && p.case_id != CFD_RAYLEIGH_BENARD) {
+    why = "multigrid covers the cavity and Rayleigh-Benard (case rule): the channel has CFD_POISSON_MULTIGRID_OPEN, "
+          "the step CFD_POISSON_MULTIGRID_STEP";
+    return false;
+  }
+  if (p.nx < 2 || p.ny < 2 || !(p.dx > 0)) {
+    why = "multigrid needs a grid of at least 2 x 2 cells and dx > 0 (grid rule)";
+    return false;
+  }
+  int nx = p.nx, ny = p.ny, n = 0;
+  plan = MgPlan{};
+  for (;;) {
+    MgLevel& L = plan.lv[n];
+    const double omega = mg_level_base(L, nx, ny);
+    L.h2 = std::ldexp(1.0, 2 * n) * (p.dx * p.dx);
+    L.ih2 = 1.0 / L.h2;
+    const double d = 0.5 + std::ldexp(1.0, -(n + 1));
+    L.cS = 1.0 / d;
+    L.g = 1.0 - L.cS;
+    for (int k = 0; k < 16; ++k) {
+      const double ew = k & 1, ee = (k >> 1) & 1, en = (k >> 2) & 1, cs = (k & 8) ? L.cS : 1.0;
+      L.rdiag[k] = 1.0 / (((ew + ee) + en) + cs);
+      L.omr[k] = omega * L.rdiag[k];
+    }
+    ++n;
+    if (!(nx % 2 == 0 && ny % 2 == 0 && std::min(nx, ny) >= 8) || n == MG_MAX_LEVELS) break;
+    nx /= 2;
+    ny /= 2;
+  }
+  return mg_finish_plan(plan, n, mg_grid_name(p) + " has no multigrid plan (grid rule): ",
+                        "a second level needs both sizes even and at least 8", why);
+}
+
 extern "C" int cfd_mg_plan(const cfd_params* p, int* levels, int* coarse_nx, int* coarse_ny) {
   if (!p) {
     cfd::set_last_error("null params");
@@ -301,13 +428,7 @@ extern "C" int cfd_mg_plan(const cfd_params* p, int* levels, int* coarse_nx, int
   return CFD_OK;
 }
 
-// The channel's plan (mg.hpp, DESIGN.md §8 "The channel"): level 0 is the
-// solver's grid with hx = dx, hy = dy. With r = (hy / hx)^2 the next level
-// halves x only (r > 2), y only (r < 1/2) or both; a direction can be halved
-// while its size is even and at least 8, and a level whose chosen direction(s)
-// cannot be halved is the coarsest. Valid with 2 .. MG_MAX_LEVELS levels and a
-// coarsest level of at most MG_COARSE_CELLS cells. The constants are formed in
-// the operations tests/mg_open_reference.py states.
+// The channel's plan (DESIGN.md §8 "The channel"): mg_semi_plan without a block.
 bool cfd::mgo_make_plan(const cfd_params& p, MgoPlan& plan, std::string& why) {
   if (p.case_id != CFD_CHANNEL) {
     why = "open multigrid covers the channel (case rule): the cavity and Rayleigh-Benard have CFD_POISSON_MULTIGRID, "
@@ -318,109 +439,15 @@ bool cfd::mgo_make_plan(const cfd_params& p, MgoPlan& plan, std::string& why) {
     why = "open multigrid needs a grid of at least 2 x 2 cells and dx, dy > 0 (grid rule)";
     return false;
   }
-  const std::string grid = "grid " + std::to_string(p.nx) + " x " + std::to_string(p.ny);
-  int nx = p.nx, ny = p.ny, a = 0, b = 0, n = 0;
-  plan = MgoPlan{};
-  for (;;) {
-    if (n == MG_MAX_LEVELS) {
-      why = grid + " has no open multigrid plan (grid rule): more than " + std::to_string(MG_MAX_LEVELS) + " levels";
-      return false;
-    }
-    MgoLevel& L = plan.lv[n];
-    L.nx = nx;
-    L.ny = ny;
-    L.pitch = ((nx + 3) + 15) / 16 * 16;  // the solver's own row pitch rule (level 0: its p and f buffers)
-    L.lds_p = L.lds_f = -1;
-    L.a = a;
-    L.b = b;
-    const int m = std::max(nx, ny);
-    L.coarse_sweeps = 4 * m;
-    const double hx = std::ldexp(p.dx, a), hy = std::ldexp(p.dy, b);
-    L.cx = 1.0 / (hx * hx);
-    L.cy = 1.0 / (hy * hy);
-    const double d = 0.5 + std::ldexp(1.0, -(a + 1));
-    L.cE = L.cx / d;
-    L.g = 1.0 - 1.0 / d;
-    const double pi = 3.14159265358979323846;
-    const double omega = 2.0 / (1.0 + std::sin(pi / (m + 1)));
-    L.one_m_omega = 1.0 - omega;
-    for (int k = 0; k < 16; ++k) {
-      const double cw = (k & 1) ? L.cx : 0.0, ce = (k & 2) ? L.cx : L.cE;
-      const double cs = (k & 4) ? L.cy : 0.0, cn = (k & 8) ? L.cy : 0.0;
-      L.rdiag[k] = 1.0 / ((cw + ce) + (cs + cn));
-      L.omr[k] = omega * L.rdiag[k];
-    }
-    ++n;
-    const double q = hy / hx, r = q * q;
-    const bool can_x = nx % 2 == 0 && nx >= 8, can_y = ny % 2 == 0 && ny >= 8;
-    L.kind = -1;
-    if (r > 2.0) {
-      if (can_x) L.kind = MGO_X;
-    } else if (r < 0.5) {
-      if (can_y) L.kind = MGO_Y;
-    } else if (can_x && can_y) {
-      L.kind = MGO_FULL;
-    }
-    if (L.kind < 0) break;
-    if (L.kind != MGO_Y) nx /= 2, ++a;
-    if (L.kind != MGO_X) ny /= 2, ++b;
-  }
-  plan.levels = n;
-  const MgoLevel& C = plan.lv[n - 1];
-  if (n < 2) {
-    why = grid + " has no open multigrid plan (grid rule): the direction its spacings choose cannot be halved "
-                 "(a size must be even and at least 8)";
-    return false;
-  }
-  if ((long long)C.nx * C.ny > MG_COARSE_CELLS) {
-    why = grid + " has no open multigrid plan (grid rule): its coarsest level " + std::to_string(C.nx) + " x " +
-          std::to_string(C.ny) + " holds more than " + std::to_string(MG_COARSE_CELLS) + " cells";
-    return false;
-  }
-  int tail = n - 1;  // the one-launch tail, by mg_make_plan's rule
-  for (int l = n - 1; l >= 1; --l) {
-    long long need = 0;
-    for (int q = l; q < n; ++q) need += 2LL * (plan.lv[q].nx + 2) * (plan.lv[q].ny + 2);
-    if ((long long)plan.lv[l].nx * plan.lv[l].ny > MG_COARSE_CELLS || need > MG_LDS_DOUBLES) break;
-    tail = l;
-  }
-  plan.tail = tail;
-  int off = 0;
-  for (int q = tail; q < n; ++q) {
-    const int cells = (plan.lv[q].nx + 2) * (plan.lv[q].ny + 2);
-    plan.lv[q].lds_p = off;
-    plan.lv[q].lds_f = off + cells;
-    off += 2 * cells;
-  }
-  return true;
+  return mg_semi_plan(p, plan, MgNoBlock{}, mg_grid_name(p) + " has no open multigrid plan (grid rule): ",
+                      "the direction its spacings choose cannot be halved (a size must be even and at least 8)", why);
 }
 
 extern "C" int cfd_mg_open_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny) {
-  if (!p) {
-    cfd::set_last_error("null params");
-    return CFD_E_ARG;
-  }
-  cfd::MgoPlan plan;
-  std::string why;
-  if (!cfd::mgo_make_plan(*p, plan, why)) {
-    cfd::set_last_error(why);
-    return CFD_E_ARG;
-  }
-  if (levels) *levels = plan.levels;
-  for (int l = 0; l < cfd::MG_MAX_LEVELS; ++l) {
-    if (level_nx) level_nx[l] = l < plan.levels ? plan.lv[l].nx : 0;
-    if (level_ny) level_ny[l] = l < plan.levels ? plan.lv[l].ny : 0;
-  }
-  return CFD_OK;
+  return mg_report_levels<cfd::MgoPlan>(p, cfd::mgo_make_plan, levels, level_nx, level_ny);
 }
 
-// The step's plan (mg.hpp): the channel's semi-coarsening rule by
-// r = (hy / hx)^2 with the block halved with the grid, si = step_i >> a and jm =
-// inlet_jmax >> b. x can be halved while nx is even and at least 8 and si is even
-// and at least 2; y while ny is even and at least 8, jm is even and at least 2 and
-// the block is at least 2 rows high - so a coarse cell's children are all fluid or
-// all solid and every level keeps the pair A = (jm+1, si+1), B = (jm, si). The
-// constants are formed in the operations tests/mg_step_reference.py states.
+// The step's plan: mg_semi_plan with the block halved along (MgStepBlock).
 bool cfd::mgs_make_plan(const cfd_params& p, MgsPlan& plan, std::string& why) {
   if (p.case_id != CFD_BACKSTEP) {
     why = "step multigrid covers the backwards-facing step (case rule): the cavity and Rayleigh-Benard have "
@@ -436,111 +463,12 @@ bool cfd::mgs_make_plan(const cfd_params& p, MgsPlan& plan, std::string& why) {
           std::to_string(p.step_i) + ", inlet_jmax " + std::to_string(p.inlet_jmax) + " of " + std::to_string(p.ny) + " rows";
     return false;
   }
-  const std::string grid = "grid " + std::to_string(p.nx) + " x " + std::to_string(p.ny);
-  int nx = p.nx, ny = p.ny, a = 0, b = 0, si = p.step_i, jm = p.inlet_jmax, n = 0;
-  plan = MgsPlan{};
-  for (;;) {
-    if (n == MG_MAX_LEVELS) {
-      why = grid + " has no step multigrid plan (grid rule): more than " + std::to_string(MG_MAX_LEVELS) + " levels";
-      return false;
-    }
-    MgsLevel& L = plan.lv[n];
-    L.nx = nx;
-    L.ny = ny;
-    L.pitch = ((nx + 3) + 15) / 16 * 16;  // the solver's own row pitch rule (level 0: its p and f buffers)
-    L.lds_p = L.lds_f = -1;
-    L.a = a;
-    L.b = b;
-    L.si = si;
-    L.jm = jm;
-    const int m = std::max(nx, ny);
-    L.coarse_sweeps = 4 * m;
-    const double hx = std::ldexp(p.dx, a), hy = std::ldexp(p.dy, b);
-    L.cx = 1.0 / (hx * hx);
-    L.cy = 1.0 / (hy * hy);
-    L.chx = L.cx * 0.5;
-    L.chy = L.cy * 0.5;
-    const double d = 0.5 + std::ldexp(1.0, -(a + 1));
-    L.cE = L.cx / d;
-    L.g = 1.0 - 1.0 / d;
-    const double pi = 3.14159265358979323846;
-    const double omega = 2.0 / (1.0 + std::sin(pi / (m + 1)));
-    L.one_m_omega = 1.0 - omega;
-    for (int k = 0; k < 16; ++k) {
-      const double cw = (k & 1) ? L.cx : 0.0, ce = (k & 2) ? L.cx : L.cE;
-      const double cs = (k & 4) ? L.cy : 0.0, cn = (k & 8) ? L.cy : 0.0;
-      L.rdiag[k] = 1.0 / ((cw + ce) + (cs + cn));
-      L.omr[k] = omega * L.rdiag[k];
-    }
-    {  // A = (jm+1, si+1): west through the corner (cx / 2), south fluid; B = (jm, si): north through it (cy / 2), east fluid
-      const double ceA = si + 1 < nx ? L.cx : L.cE, cnA = jm + 1 < ny ? L.cy : 0.0;
-      L.rdA = 1.0 / ((L.chx + ceA) + (L.cy + cnA));
-      const double cwB = si > 1 ? L.cx : 0.0, ceB = si < nx ? L.cx : L.cE, csB = jm > 1 ? L.cy : 0.0;
-      L.rdB = 1.0 / ((cwB + ceB) + (csB + L.chy));
-      L.omrA = omega * L.rdA;
-      L.omrB = omega * L.rdB;
-    }
-    ++n;
-    const double q = hy / hx, r = q * q;
-    const bool can_x = nx % 2 == 0 && nx >= 8 && si % 2 == 0 && si >= 2;
-    const bool can_y = ny % 2 == 0 && ny >= 8 && jm % 2 == 0 && jm >= 2 && ny - jm >= 2;
-    L.kind = -1;
-    if (r > 2.0) {
-      if (can_x) L.kind = MGO_X;
-    } else if (r < 0.5) {
-      if (can_y) L.kind = MGO_Y;
-    } else if (can_x && can_y) {
-      L.kind = MGO_FULL;
-    }
-    if (L.kind < 0) break;
-    if (L.kind != MGO_Y) nx /= 2, si /= 2, ++a;
-    if (L.kind != MGO_X) ny /= 2, jm /= 2, ++b;
-  }
-  plan.levels = n;
-  const MgsLevel& C = plan.lv[n - 1];
-  if (n < 2) {
-    why = grid + " has no step multigrid plan (grid rule): the direction its spacings choose cannot be halved "
-                 "(a size must be even and at least 8, the block's edge even and at least 2)";
-    return false;
-  }
-  if ((long long)C.nx * C.ny > MG_COARSE_CELLS) {
-    why = grid + " has no step multigrid plan (grid rule): its coarsest level " + std::to_string(C.nx) + " x " +
-          std::to_string(C.ny) + " holds more than " + std::to_string(MG_COARSE_CELLS) + " cells";
-    return false;
-  }
-  int tail = n - 1;  // the one-launch tail, by mg_make_plan's rule
-  for (int l = n - 1; l >= 1; --l) {
-    long long need = 0;
-    for (int q = l; q < n; ++q) need += 2LL * (plan.lv[q].nx + 2) * (plan.lv[q].ny + 2);
-    if ((long long)plan.lv[l].nx * plan.lv[l].ny > MG_COARSE_CELLS || need > MG_LDS_DOUBLES) break;
-    tail = l;
-  }
-  plan.tail = tail;
-  int off = 0;
-  for (int q = tail; q < n; ++q) {
-    const int cells = (plan.lv[q].nx + 2) * (plan.lv[q].ny + 2);
-    plan.lv[q].lds_p = off;
-    plan.lv[q].lds_f = off + cells;
-    off += 2 * cells;
-  }
-  return true;
+  return mg_semi_plan(p, plan, MgStepBlock{p.step_i, p.inlet_jmax}, mg_grid_name(p) + " has no step multigrid plan (grid rule): ",
+                      "the direction its spacings choose cannot be halved (a size must be even and at least 8, the block's "
+                      "edge even and at least 2)",
+                      why);
 }
 
 extern "C" int cfd_mg_step_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny) {
-  if (!p) {
-    cfd::set_last_error("null params");
-    return CFD_E_ARG;
-  }
-  cfd::MgsPlan plan;
-  std::string why;
-  if (!cfd::mgs_make_plan(*p, plan, why)) {
-    cfd::set_last_error(why);
-    return CFD_E_ARG;
-  }
-  if (levels) *levels = plan.levels;
-  for (int l = 0; l < cfd::MG_MAX_LEVELS; ++l) {
-    if (level_nx) level_nx[l] = l < plan.levels ? plan.lv[l].nx : 0;
-    if (level_ny) level_ny[l] = l < plan.levels ? plan.lv[l].ny : 0;
-  }
-  return CFD_OK;
+  return mg_report_levels<cfd::MgsPlan>(p, cfd::mgs_make_plan, levels, level_nx, level_ny);
 }

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "internal.hpp"
@@ -1688,10 +1689,12 @@ class Solver {
   }
 
   // ---------------------------------------------------------- multigrid --
-  // The opt-in multigrid solve (mg.hpp): cfd_set_poisson_method.
-  bool mg_on = false;
-  MgPlan mgp;
-  MgLevel* mg_dlv = nullptr;            // the plan's levels in device memory
+  // The opt-in multigrid solve (mg.hpp): cfd_set_poisson_method. One driver serves the three
+  // schemes (the cavity's, the channel's, the step's): the launches are mg.hip's templates over the plan's
+  // level type, and what a solve does differently by scheme is in the three hooks solve_mg hands to mg_solve.
+  int mg_method = CFD_POISSON_SOR;                 // the active method (SOR: none of the state below)
+  std::variant<MgPlan, MgoPlan, MgsPlan> mg_plan;  // its plan: the alternative mg_method names
+  void* mg_dlv = nullptr;                          // the plan's levels in device memory
   std::vector<double*> mg_p, mg_f;      // levels >= 1: correction and source, rows 0 .. ny+1 of lv.pitch doubles
   // Fused smoothing (mg_smooth_tile_kernel) writes to a second buffer: mg_q[l] for the multi-launch levels
   // (level 0: mg_q0, laid out like the strip's p buffers, mg_q[0] its row 0); mg_cur[l] is the one that holds
@@ -1703,14 +1706,6 @@ class Solver {
   int mg_nu1 = 2, mg_nu2 = 2, mg_max_cycles = 50;
   cfd_mg_info mgi{};
   hipEvent_t mg_ev[4] = {};             // around the level-0 launches of a cycle's way down / way up
-  // CFD_POISSON_MULTIGRID_OPEN, the channel's scheme: its own plan and kernels (mgo_*), the buffers above
-  bool mgo_on = false;
-  MgoPlan mgop;
-  MgoLevel* mgo_dlv = nullptr;
-  // CFD_POISSON_MULTIGRID_STEP, the backwards-facing step's scheme: its own plan and kernels (mgs_*), the buffers above
-  bool mgs_on = false;
-  MgsPlan mgsp;
-  MgsLevel* mgs_dlv = nullptr;
 
   void mg_release() noexcept {
     for (double* q : mg_p)
@@ -1727,17 +1722,11 @@ class Solver {
     mg_cur.clear();
     if (mg_dlv) (void)hipFree(mg_dlv);
     mg_dlv = nullptr;
-    if (mgo_dlv) (void)hipFree(mgo_dlv);
-    mgo_dlv = nullptr;
-    mgo_on = false;
-    if (mgs_dlv) (void)hipFree(mgs_dlv);
-    mgs_dlv = nullptr;
-    mgs_on = false;
     for (auto& e : mg_ev) {
       if (e) (void)hipEventDestroy(e);
       e = nullptr;
     }
-    mg_on = false;
+    mg_method = CFD_POISSON_SOR;
   }
 
   void set_poisson_method(int method, const cfd_mg_options* opt) {
@@ -1747,45 +1736,36 @@ class Solver {
       mgi.levels = mgi.coarse_nx = mgi.coarse_ny = mgi.coarse_sweeps = 0;
       return;
     }
-    const bool open = method == CFD_POISSON_MULTIGRID_OPEN;  // the channel's scheme (mg.hpp "the channel")
-    const bool stepm = method == CFD_POISSON_MULTIGRID_STEP;  // the step's scheme (mg.hpp "the step")
-    if (method != CFD_POISSON_MULTIGRID && !open && !stepm) throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
+    if (method != CFD_POISSON_MULTIGRID && method != CFD_POISSON_MULTIGRID_OPEN && method != CFD_POISSON_MULTIGRID_STEP)
+      throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
     if (S.size() != 1) throw Error(CFD_E_ARG, "multigrid runs on one strip (strip rule): this solver has n_strips > 1");
     if (comm) throw Error(CFD_E_ARG, "multigrid runs without ranks (rank rule): this is a rank solver");
     const int nu1 = opt && opt->pre_sweeps ? opt->pre_sweeps : 2, nu2 = opt && opt->post_sweeps ? opt->post_sweeps : 2;
     const int mc = opt && opt->max_cycles ? opt->max_cycles : 50;
     if (nu1 < 0 || nu2 < 0 || nu1 + nu2 < 1 || mc < 1)
       throw Error(CFD_E_ARG, "multigrid options: sweeps must be >= 0 with at least one per cycle, max_cycles >= 1");
-    MgPlan plan;
-    MgoPlan oplan;
-    MgsPlan splan;
+    if (method == CFD_POISSON_MULTIGRID_STEP) mg_install<MgsPlan>(method, mgs_make_plan);
+    else if (method == CFD_POISSON_MULTIGRID_OPEN) mg_install<MgoPlan>(method, mgo_make_plan);
+    else mg_install<MgPlan>(method, mg_make_plan);
+    mg_nu1 = nu1;
+    mg_nu2 = nu2;
+    mg_max_cycles = mc;
+  }
+
+  // makes `method`'s plan of this solver's parameters the active one: its device copy, the level buffers, the events
+  template <class Plan>
+  void mg_install(int method, bool (*make)(const cfd_params&, Plan&, std::string&)) {
+    Plan plan;
     std::string why;
-    if (stepm ? !mgs_make_plan(P, splan, why) : open ? !mgo_make_plan(P, oplan, why) : !mg_make_plan(P, plan, why))
-      throw Error(CFD_E_ARG, why);
-    if ((stepm ? splan.lv[0].pitch : open ? oplan.lv[0].pitch : plan.lv[0].pitch) != pitch)
-      throw Error(CFD_E_STATE, "multigrid plan pitch differs from the solver's");
-    const int levels = stepm ? splan.levels : open ? oplan.levels : plan.levels;
-    const int tail = stepm ? splan.tail : open ? oplan.tail : plan.tail;
-    auto level_bytes = [&](int l) {
-      return stepm  ? (size_t)(splan.lv[l].ny + 2) * splan.lv[l].pitch * sizeof(double)
-             : open ? (size_t)(oplan.lv[l].ny + 2) * oplan.lv[l].pitch * sizeof(double)
-                    : (size_t)(plan.lv[l].ny + 2) * plan.lv[l].pitch * sizeof(double);
-    };
+    if (!make(P, plan, why)) throw Error(CFD_E_ARG, why);
+    if (plan.lv[0].pitch != pitch) throw Error(CFD_E_STATE, "multigrid plan pitch differs from the solver's");
+    const int levels = plan.levels, tail = plan.tail;
+    auto level_bytes = [&](int l) { return (size_t)(plan.lv[l].ny + 2) * plan.lv[l].pitch * sizeof(double); };
     HIPC(hipStreamSynchronize(st));
     mg_release();
-    if (stepm) {
-      mgsp = splan;
-      HIPC(hipMalloc(&mgs_dlv, sizeof(MgsLevel) * MG_MAX_LEVELS));
-      HIPC(hipMemcpy(mgs_dlv, mgsp.lv, sizeof(MgsLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
-    } else if (open) {
-      mgop = oplan;
-      HIPC(hipMalloc(&mgo_dlv, sizeof(MgoLevel) * MG_MAX_LEVELS));
-      HIPC(hipMemcpy(mgo_dlv, mgop.lv, sizeof(MgoLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
-    } else {
-      mgp = plan;
-      HIPC(hipMalloc(&mg_dlv, sizeof(MgLevel) * MG_MAX_LEVELS));
-      HIPC(hipMemcpy(mg_dlv, mgp.lv, sizeof(MgLevel) * MG_MAX_LEVELS, hipMemcpyHostToDevice));
-    }
+    mg_plan = plan;
+    HIPC(hipMalloc(&mg_dlv, sizeof(plan.lv)));
+    HIPC(hipMemcpy(mg_dlv, plan.lv, sizeof(plan.lv), hipMemcpyHostToDevice));
     mg_p.assign(levels, nullptr);
     mg_f.assign(levels, nullptr);
     for (int l = 1; l <= tail; ++l) {  // (levels below the tail's first live in LDS only)
@@ -1811,22 +1791,19 @@ class Solver {
       }
     }
     for (auto& e : mg_ev) HIPC(hipEventCreate(&e));
-    mg_nu1 = nu1;
-    mg_nu2 = nu2;
-    mg_max_cycles = mc;
     mgi.levels = levels;
-    mgi.coarse_nx = stepm ? splan.lv[levels - 1].nx : open ? oplan.lv[levels - 1].nx : plan.lv[levels - 1].nx;
-    mgi.coarse_ny = stepm ? splan.lv[levels - 1].ny : open ? oplan.lv[levels - 1].ny : plan.lv[levels - 1].ny;
-    mgi.coarse_sweeps = stepm  ? splan.lv[levels - 1].coarse_sweeps
-                        : open ? oplan.lv[levels - 1].coarse_sweeps
-                               : plan.lv[levels - 1].coarse_sweeps;
-    (stepm ? mgs_on : open ? mgo_on : mg_on) = true;
+    mgi.coarse_nx = plan.lv[levels - 1].nx;
+    mgi.coarse_ny = plan.lv[levels - 1].ny;
+    mgi.coarse_sweeps = plan.lv[levels - 1].coarse_sweeps;
+    mg_method = method;
   }
 
-  // one V-cycle from level 0 on mg_cur[0] (p0: row 0 of the solver's p buffer) / f0; returns its launches
-  int mg_vcycle(double* p0, const double* f0) {
+  // one V-cycle from level 0 on mg_cur[0] (p0: row 0 of the solver's p buffer) / f0; returns its launches.
+  // Each transfer is by its fine level (the semi-coarsened schemes: its kind).
+  template <class Plan>
+  int mg_vcycle(const Plan& plan, double* p0, const double* f0) {
+    const auto* dlv = static_cast<decltype(&plan.lv[0])>(mg_dlv);
     int launches = 0;
-    auto P_ = [&](int l) { return mg_cur[l]; };
     auto F_ = [&](int l) { return l == 0 ? f0 : (const double*)mg_f[l]; };
     auto smooth = [&](int l, int n) {
       if (mg_fused) {  // up to 3 sweeps per launch, into the level's other buffer
@@ -1834,7 +1811,7 @@ class Solver {
           const int k = left == 4 ? 2 : std::min(left, 3);
           double* a = l == 0 ? p0 : mg_p[l];
           double* other = mg_cur[l] == a ? mg_q[l] : a;
-          mg_smooth_tile_launch(mg_dlv, mgp.lv[l], l, mg_cur[l], other, F_(l), k, st);
+          mg_smooth_tile_launch(dlv, plan.lv[l], l, mg_cur[l], other, F_(l), k, st);
           check_launch("mg_smooth_tile");
           ++launches;
           mg_cur[l] = other;
@@ -1844,27 +1821,27 @@ class Solver {
       }
       for (int q = 0; q < n; ++q)
         for (int colour = 0; colour < 2; ++colour) {
-          mg_smooth_launch(mg_dlv, mgp.lv[l], l, P_(l), F_(l), colour, st);
+          mg_smooth_launch(dlv, plan.lv[l], l, mg_cur[l], F_(l), colour, st);
           check_launch("mg_smooth");
           ++launches;
         }
     };
-    const int tail = mgp.tail, last = mgp.levels - 1;
+    const int tail = plan.tail, last = plan.levels - 1;
     HIPC(hipEventRecord(mg_ev[0], st));
     for (int l = 0; l < tail; ++l) {
       smooth(l, mg_nu1);
       mg_cur[l + 1] = mg_p[l + 1];
-      mg_restrict_launch(mg_dlv, mgp.lv[l + 1], l, P_(l), F_(l), mg_f[l + 1], mg_p[l + 1], st);
+      mg_restrict_launch(dlv, plan.lv[l + 1], l, mg_cur[l], F_(l), mg_f[l + 1], mg_p[l + 1], st);
       check_launch("mg_restrict");
       ++launches;
       if (l == 0) HIPC(hipEventRecord(mg_ev[1], st));
     }
-    mg_tail_launch(mg_dlv, tail, last, mg_nu1, mg_nu2, mg_f[tail], mg_p[tail], st);
+    mg_tail_launch(dlv, tail, last, mg_nu1, mg_nu2, mg_f[tail], mg_p[tail], st);
     check_launch("mg_tail");
     ++launches;
     for (int l = tail - 1; l >= 0; --l) {
       if (l == 0) HIPC(hipEventRecord(mg_ev[2], st));
-      mg_prolong_launch(mg_dlv, mgp.lv[l], l, P_(l), mg_cur[l + 1], st);
+      mg_prolong_launch(dlv, plan.lv[l], l, mg_cur[l], mg_cur[l + 1], st);
       check_launch("mg_prolong");
       ++launches;
       smooth(l, mg_nu2);
@@ -1873,11 +1850,63 @@ class Solver {
     return launches;
   }
 
-  // max-norm residual (cavity-01.cpp:659-677) of the field in a buffer laid out like the strip's (final_residual's pass)
-  double mg_residual(const double* buf) {
+  // The solve of every scheme: V-cycles until the reference's max-norm residual meets its tolerance (or
+  // mg_max_cycles). The hooks: start(X, tol) prepares the field and returns the residual the loop is primed
+  // with; after_cycle(buf, launches) refreshes what the reference refreshes in the cycle's field (mg_cur[0],
+  // in the buffer `buf` laid out like the strip's), counts its launches and returns the residual; copy_back(p0,
+  // q) brings the field home after an odd number of fused launches left it in the second buffer.
+  template <class Plan, class Start, class AfterCycle, class CopyBack>
+  void mg_solve(const Plan& plan, cfd_step_info* out, Start start, AfterCycle after_cycle, CopyBack copy_back) {
     Strip& s = S[0];
+    double* X = s.b[pbuf(pcur)];
+    solve_tolerance();
+    const double tol = tol_host();
+    double* p0 = X + (size_t)(0 - s.g.row_lo) * pitch;
+    const double* f0 = s.b[B_F] + (size_t)(0 - s.g.row_lo) * pitch;
+    double res = start(X, tol);
+    HIPC(hipEventRecord(ev_a, st));
+    int cycles = 0;
+    long long launches = 0;
+    double fine = 0.0;
+    mg_cur[0] = p0;
+    while (res > tol && cycles < mg_max_cycles) {
+      launches += mg_vcycle(plan, p0, f0);
+      res = after_cycle(mg_cur[0] == p0 ? X : mg_q0, launches);  // (waits for the stream)
+      ++cycles;
+      float a = 0.f, b = 0.f;
+      HIPC(hipEventElapsedTime(&a, mg_ev[0], mg_ev[1]));
+      HIPC(hipEventElapsedTime(&b, mg_ev[2], mg_ev[3]));
+      fine += (double)a + (double)b;
+    }
+    if (mg_cur[0] != p0) {
+      copy_back(p0, mg_cur[0]);
+      mg_cur[0] = p0;
+    }
+    HIPC(hipEventRecord(ev_b, st));
+    HIPC(hipEventSynchronize(ev_b));
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
+    const long long sweeps = (long long)cycles * (mg_nu1 + mg_nu2);
+    T.poisson_ms += ms;
+    T.poisson_launches += launches;
+    T.poisson_sweeps += sweeps;  // (level-0 sweeps)
+    T.poisson_cell_updates += (long long)P.nx * P.ny * sweeps;
+    mgi.solves += 1;
+    mgi.cycles += cycles;
+    mgi.launches += launches;
+    mgi.solve_ms += ms;
+    mgi.fine_ms += fine;
+    if (out) {
+      out->sor_iterations = cycles;
+      out->residual = res;
+    }
+  }
+
+  // the max over the shards of the residual pass `launch` enqueues (waits for the stream)
+  template <class Launch>
+  double mg_resmax(Launch launch) {
     HIPC(hipMemsetAsync(resmax, 0, RES_SHARDS * SHARD_STRIDE * sizeof(double), st));
-    cavity_resmax_kernel<<<pair_grid(s), 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax);
+    launch();
     check_launch("resmax");
     HIPC(hipMemcpyAsync(h_shard, resmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -1886,299 +1915,79 @@ class Solver {
     return res;
   }
 
+  // an open case's own max-norm residual, on the ghosts the buffer holds
+  template <int CASE>
+  double mg_open_residual(const double* buf) {
+    Strip& s = S[0];
+    const int rrows = std::min(s.g.j1, P.ny) - std::max(s.g.j0, 1) + 1;
+    const dim3 rgrid((P.nx + 63) / 64, std::max(1, (rrows + 3) / 4));
+    return mg_resmax([&] { open_resmax_kernel<CASE><<<rgrid, 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax); });
+  }
+
   void solve_mg(cfd_step_info* out) {
     Strip& s = S[0];
-    double* X = s.b[pbuf(pcur)];
-    // cavity-01.cpp:610-611: each solve starts from a zero field, ghosts included
-    HIPC(hipMemsetAsync(X, 0, (size_t)s.g.nrows * pitch * sizeof(double), st));
-    solve_tolerance();
-    const double tol = tol_host();
-    double* p0 = X + (size_t)(0 - s.g.row_lo) * pitch;
-    const double* f0 = s.b[B_F] + (size_t)(0 - s.g.row_lo) * pitch;
-    HIPC(hipEventRecord(ev_a, st));
-    double res = 1.0;  // cavity-01.cpp:618
-    int cycles = 0;
-    long long launches = 0;
-    double fine = 0.0;
-    mg_cur[0] = p0;
-    while (res > tol && cycles < mg_max_cycles) {
-      launches += mg_vcycle(p0, f0);
-      // the reference's max-norm residual of the cycle's field (waits for the stream)
-      res = mg_residual(mg_cur[0] == p0 ? X : mg_q0);
-      launches += 1;
-      ++cycles;
-      float a = 0.f, b = 0.f;
-      HIPC(hipEventElapsedTime(&a, mg_ev[0], mg_ev[1]));
-      HIPC(hipEventElapsedTime(&b, mg_ev[2], mg_ev[3]));
-      fine += (double)a + (double)b;
-    }
-    if (mg_cur[0] != p0) {  // (an odd number of fused launches: the field is in the second buffer)
-      HIPC(hipMemcpyAsync(p0, mg_cur[0], (size_t)(P.ny + 2) * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
-      mg_cur[0] = p0;
-    }
-    HIPC(hipEventRecord(ev_b, st));
-    HIPC(hipEventSynchronize(ev_b));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    const long long sweeps = (long long)cycles * (mg_nu1 + mg_nu2);
-    T.poisson_ms += ms;
-    T.poisson_launches += launches;
-    T.poisson_sweeps += sweeps;  // (level-0 sweeps)
-    T.poisson_cell_updates += (long long)P.nx * P.ny * sweeps;
-    mgi.solves += 1;
-    mgi.cycles += cycles;
-    mgi.launches += launches;
-    mgi.solve_ms += ms;
-    mgi.fine_ms += fine;
-    if (out) {
-      out->sor_iterations = cycles;
-      out->residual = res;
-    }
-  }
-
-  // The channel's V-cycle (mg_vcycle with the mgo_* launches; each transfer's kind is level l's).
-  int mgo_vcycle(double* p0, const double* f0) {
-    int launches = 0;
-    auto F_ = [&](int l) { return l == 0 ? f0 : (const double*)mg_f[l]; };
-    auto smooth = [&](int l, int n) {
-      if (mg_fused) {  // up to 3 sweeps per launch, into the level's other buffer
-        for (int left = n; left > 0;) {
-          const int k = left == 4 ? 2 : std::min(left, 3);
-          double* a = l == 0 ? p0 : mg_p[l];
-          double* other = mg_cur[l] == a ? mg_q[l] : a;
-          mgo_smooth_tile_launch(mgo_dlv, mgop.lv[l], l, mg_cur[l], other, F_(l), k, st);
-          check_launch("mgo_smooth_tile");
-          ++launches;
-          mg_cur[l] = other;
-          left -= k;
-        }
-        return;
-      }
-      for (int q = 0; q < n; ++q)
-        for (int colour = 0; colour < 2; ++colour) {
-          mgo_smooth_launch(mgo_dlv, mgop.lv[l], l, mg_cur[l], F_(l), colour, st);
-          check_launch("mgo_smooth");
-          ++launches;
-        }
-    };
-    const int tail = mgop.tail, last = mgop.levels - 1;
-    HIPC(hipEventRecord(mg_ev[0], st));
-    for (int l = 0; l < tail; ++l) {
-      smooth(l, mg_nu1);
-      mg_cur[l + 1] = mg_p[l + 1];
-      mgo_restrict_launch(mgo_dlv, mgop.lv[l + 1], l, mg_cur[l], F_(l), mg_f[l + 1], mg_p[l + 1], st);
-      check_launch("mgo_restrict");
-      ++launches;
-      if (l == 0) HIPC(hipEventRecord(mg_ev[1], st));
-    }
-    mgo_tail_launch(mgo_dlv, tail, last, mg_nu1, mg_nu2, mg_f[tail], mg_p[tail], st);
-    check_launch("mgo_tail");
-    ++launches;
-    for (int l = tail - 1; l >= 0; --l) {
-      if (l == 0) HIPC(hipEventRecord(mg_ev[2], st));
-      mgo_prolong_launch(mgo_dlv, mgop.lv[l], l, mg_cur[l], mg_cur[l + 1], st);
-      check_launch("mgo_prolong");
-      ++launches;
-      smooth(l, mg_nu2);
-    }
-    HIPC(hipEventRecord(mg_ev[3], st));
-    return launches;
-  }
-
-  // The channel's solve (channel-01.cpp:642-688 with a V-cycle for the sweep): a warm start from the
-  // field the solver holds, the loop primed with tol + 1, after each cycle the reference's ghost
-  // refresh and its own max-norm residual on those ghosts.
-  void solve_mg_open(cfd_step_info* out) {
-    Strip& s = S[0];
-    double* X = s.b[pbuf(pcur)];
-    solve_tolerance();
-    const double tol = tol_host();
-    double* p0 = X + (size_t)(0 - s.g.row_lo) * pitch;
-    const double* f0 = s.b[B_F] + (size_t)(0 - s.g.row_lo) * pitch;
-    const int rrows = std::min(s.g.j1, P.ny) - std::max(s.g.j0, 1) + 1;
-    const dim3 rgrid((P.nx + 63) / 64, std::max(1, (rrows + 3) / 4));
-    HIPC(hipEventRecord(ev_a, st));
-    double res = tol + 1.0;  // channel-01.cpp:650
-    int cycles = 0;
-    long long launches = 0;
-    double fine = 0.0;
-    mg_cur[0] = p0;
-    while (res > tol && cycles < mg_max_cycles) {
-      launches += mgo_vcycle(p0, f0);
-      double* buf = mg_cur[0] == p0 ? X : mg_q0;
-      res_refresh(s.g, buf, st);  // channel-01.cpp:531-541: west and east columns, then south and north rows
-      check_launch("mgo_refresh");
-      HIPC(hipMemsetAsync(resmax, 0, RES_SHARDS * SHARD_STRIDE * sizeof(double), st));
-      open_resmax_kernel<CHANNEL><<<rgrid, 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax);
-      check_launch("resmax");
-      HIPC(hipMemcpyAsync(h_shard, resmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIPC(hipStreamSynchronize(st));
-      res = 0.0;
-      for (int q = 0; q < RES_SHARDS; ++q) res = std::max(res, h_shard[q * SHARD_STRIDE]);
-      launches += 2;
-      ++cycles;
-      float a = 0.f, b = 0.f;
-      HIPC(hipEventElapsedTime(&a, mg_ev[0], mg_ev[1]));
-      HIPC(hipEventElapsedTime(&b, mg_ev[2], mg_ev[3]));
-      fine += (double)a + (double)b;
-    }
-    if (mg_cur[0] != p0) {
-      // an odd number of fused launches: the field is in the second buffer. Rows 1 .. ny whole (their
-      // ghost columns are refreshed), the ghost rows over columns 1 .. nx: the corners stay p's own.
-      const double* q = mg_cur[0];
-      HIPC(hipMemcpyAsync(p0 + pitch, q + pitch, (size_t)P.ny * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
-      HIPC(hipMemcpyAsync(p0 + 1, q + 1, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      const size_t top = (size_t)(P.ny + 1) * pitch + 1;
-      HIPC(hipMemcpyAsync(p0 + top, q + top, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      mg_cur[0] = p0;
-    }
-    HIPC(hipEventRecord(ev_b, st));
-    HIPC(hipEventSynchronize(ev_b));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    const long long sweeps = (long long)cycles * (mg_nu1 + mg_nu2);
-    T.poisson_ms += ms;
-    T.poisson_launches += launches;
-    T.poisson_sweeps += sweeps;  // (level-0 sweeps)
-    T.poisson_cell_updates += (long long)P.nx * P.ny * sweeps;
-    mgi.solves += 1;
-    mgi.cycles += cycles;
-    mgi.launches += launches;
-    mgi.solve_ms += ms;
-    mgi.fine_ms += fine;
-    if (out) {
-      out->sor_iterations = cycles;
-      out->residual = res;
-    }
-  }
-
-  // The step's V-cycle (mgo_vcycle with the mgs_* launches).
-  int mgs_vcycle(double* p0, const double* f0) {
-    int launches = 0;
-    auto F_ = [&](int l) { return l == 0 ? f0 : (const double*)mg_f[l]; };
-    auto smooth = [&](int l, int n) {
-      if (mg_fused) {  // up to 3 sweeps per launch, into the level's other buffer
-        for (int left = n; left > 0;) {
-          const int k = left == 4 ? 2 : std::min(left, 3);
-          double* a = l == 0 ? p0 : mg_p[l];
-          double* other = mg_cur[l] == a ? mg_q[l] : a;
-          mgs_smooth_tile_launch(mgs_dlv, mgsp.lv[l], l, mg_cur[l], other, F_(l), k, st);
-          check_launch("mgs_smooth_tile");
-          ++launches;
-          mg_cur[l] = other;
-          left -= k;
-        }
-        return;
-      }
-      for (int q = 0; q < n; ++q)
-        for (int colour = 0; colour < 2; ++colour) {
-          mgs_smooth_launch(mgs_dlv, mgsp.lv[l], l, mg_cur[l], F_(l), colour, st);
-          check_launch("mgs_smooth");
-          ++launches;
-        }
-    };
-    const int tail = mgsp.tail, last = mgsp.levels - 1;
-    HIPC(hipEventRecord(mg_ev[0], st));
-    for (int l = 0; l < tail; ++l) {
-      smooth(l, mg_nu1);
-      mg_cur[l + 1] = mg_p[l + 1];
-      mgs_restrict_launch(mgs_dlv, mgsp.lv[l + 1], l, mg_cur[l], F_(l), mg_f[l + 1], mg_p[l + 1], st);
-      check_launch("mgs_restrict");
-      ++launches;
-      if (l == 0) HIPC(hipEventRecord(mg_ev[1], st));
-    }
-    mgs_tail_launch(mgs_dlv, tail, last, mg_nu1, mg_nu2, mg_f[tail], mg_p[tail], st);
-    check_launch("mgs_tail");
-    ++launches;
-    for (int l = tail - 1; l >= 0; --l) {
-      if (l == 0) HIPC(hipEventRecord(mg_ev[2], st));
-      mgs_prolong_launch(mgs_dlv, mgsp.lv[l], l, mg_cur[l], mg_cur[l + 1], st);
-      check_launch("mgs_prolong");
-      ++launches;
-      smooth(l, mg_nu2);
-    }
-    HIPC(hipEventRecord(mg_ev[3], st));
-    return launches;
-  }
-
-  // The step's solve (backwards_step-01.cpp:872-939 with a V-cycle for the sweep): a warm start from the
-  // field the solver holds, the loop primed with tol + 1, after each cycle the reference's ghost and
-  // solid refresh (685-740) and its own max-norm residual over the fluid cells.
-  void solve_mg_step(cfd_step_info* out) {
-    Strip& s = S[0];
-    double* X = s.b[pbuf(pcur)];
-    solve_tolerance();
-    const double tol = tol_host();
-    double* p0 = X + (size_t)(0 - s.g.row_lo) * pitch;
-    const double* f0 = s.b[B_F] + (size_t)(0 - s.g.row_lo) * pitch;
-    const int rrows = std::min(s.g.j1, P.ny) - std::max(s.g.j0, 1) + 1;
-    const dim3 rgrid((P.nx + 63) / 64, std::max(1, (rrows + 3) / 4));
-    HIPC(hipEventRecord(ev_a, st));
-    double res = tol + 1.0;  // backwards_step-01.cpp:890
-    int cycles = 0;
-    long long launches = 0;
-    double fine = 0.0;
-    mg_cur[0] = p0;
-    const double* prev = p0;  // the buffer whose face cells hold the last refresh (before the first: p's own)
-    while (res > tol && cycles < mg_max_cycles) {
-      launches += mgs_vcycle(p0, f0);
-      double* buf = mg_cur[0] == p0 ? X : mg_q0;
-      mgs_refresh_launch(mgsp.lv[0], mg_cur[0], prev, p0, st);
-      check_launch("mgs_refresh");
-      prev = mg_cur[0];
-      HIPC(hipMemsetAsync(resmax, 0, RES_SHARDS * SHARD_STRIDE * sizeof(double), st));
-      open_resmax_kernel<BACKSTEP><<<rgrid, 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax);
-      check_launch("resmax");
-      HIPC(hipMemcpyAsync(h_shard, resmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIPC(hipStreamSynchronize(st));
-      res = 0.0;
-      for (int q = 0; q < RES_SHARDS; ++q) res = std::max(res, h_shard[q * SHARD_STRIDE]);
-      launches += 2;
-      ++cycles;
-      float a = 0.f, b = 0.f;
-      HIPC(hipEventElapsedTime(&a, mg_ev[0], mg_ev[1]));
-      HIPC(hipEventElapsedTime(&b, mg_ev[2], mg_ev[3]));
-      fine += (double)a + (double)b;
-    }
-    if (mg_cur[0] != p0) {
-      // an odd number of fused launches: the field is in the second buffer. Everything but the four
-      // corner ghosts and the interior solid cells, which stay p's own (the second buffer never held them).
-      mgs_copy_back_launch(mgsp.lv[0], p0, mg_cur[0], st);
-      check_launch("mgs_copy_back");
-      mg_cur[0] = p0;
-    }
-    HIPC(hipEventRecord(ev_b, st));
-    HIPC(hipEventSynchronize(ev_b));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    const long long sweeps = (long long)cycles * (mg_nu1 + mg_nu2);
-    T.poisson_ms += ms;
-    T.poisson_launches += launches;
-    T.poisson_sweeps += sweeps;  // (level-0 sweeps)
-    T.poisson_cell_updates += (long long)P.nx * P.ny * sweeps;
-    mgi.solves += 1;
-    mgi.cycles += cycles;
-    mgi.launches += launches;
-    mgi.solve_ms += ms;
-    mgi.fine_ms += fine;
-    if (out) {
-      out->sor_iterations = cycles;
-      out->residual = res;
+    auto warm = [](double*, double tol) { return tol + 1.0; };  // channel-01.cpp:650, backwards_step-01.cpp:890
+    if (mg_method == CFD_POISSON_MULTIGRID) {
+      // cavity-01.cpp:610-618: each solve starts from a zero field, ghosts included, and res = 1; after a cycle
+      // the reference's max-norm residual (659-677, final_residual's pass); the whole field is copied back
+      mg_solve(
+          std::get<MgPlan>(mg_plan), out,
+          [&](double* X, double) {
+            HIPC(hipMemsetAsync(X, 0, (size_t)s.g.nrows * pitch * sizeof(double), st));
+            return 1.0;
+          },
+          [&](double* buf, long long& launches) {
+            launches += 1;
+            return mg_resmax([&] { cavity_resmax_kernel<<<pair_grid(s), 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax); });
+          },
+          [&](double* p0, const double* q) {
+            HIPC(hipMemcpyAsync(p0, q, (size_t)(P.ny + 2) * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
+          });
+    } else if (mg_method == CFD_POISSON_MULTIGRID_OPEN) {
+      // channel-01.cpp:642-688 with a V-cycle for the sweep: a warm start from the field the solver holds; after
+      // a cycle the reference's ghost refresh (531-541: west and east columns, then south and north rows) and its
+      // own residual on those ghosts. Copied back: rows 1 .. ny whole (their ghost columns are refreshed), the
+      // ghost rows over columns 1 .. nx - the corners stay p's own.
+      mg_solve(
+          std::get<MgoPlan>(mg_plan), out, warm,
+          [&](double* buf, long long& launches) {
+            res_refresh(s.g, buf, st);
+            check_launch("mg_refresh");
+            launches += 2;
+            return mg_open_residual<CHANNEL>(buf);
+          },
+          [&](double* p0, const double* q) {
+            HIPC(hipMemcpyAsync(p0 + pitch, q + pitch, (size_t)P.ny * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
+            HIPC(hipMemcpyAsync(p0 + 1, q + 1, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+            const size_t top = (size_t)(P.ny + 1) * pitch + 1;
+            HIPC(hipMemcpyAsync(p0 + top, q + top, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+          });
+    } else {
+      // backwards_step-01.cpp:872-939 with a V-cycle for the sweep: a warm start; after a cycle the reference's
+      // ghost and solid refresh (685-740) and its own residual over the fluid cells. Copied back: everything
+      // but the four corner ghosts and the interior solid cells, which stay p's own (the second buffer never
+      // held them).
+      const MgsLevel& L0 = std::get<MgsPlan>(mg_plan).lv[0];
+      double* const own = s.b[pbuf(pcur)] + (size_t)(0 - s.g.row_lo) * pitch;
+      const double* prev = own;  // the buffer whose face cells hold the last refresh (before the first: p's own)
+      mg_solve(
+          std::get<MgsPlan>(mg_plan), out, warm,
+          [&](double* buf, long long& launches) {
+            mgs_refresh_launch(L0, mg_cur[0], prev, own, st);
+            check_launch("mgs_refresh");
+            prev = mg_cur[0];
+            launches += 2;
+            return mg_open_residual<BACKSTEP>(buf);
+          },
+          [&](double* p0, const double* q) {
+            mgs_copy_back_launch(L0, p0, q, st);
+            check_launch("mgs_copy_back");
+          });
     }
   }
 
   void solve(cfd_step_info* out) {
-    if (mgs_on) {
-      T.sor_kernel = CFD_SOR_MULTIGRID;
-      solve_mg_step(out);
-      return;
-    }
-    if (mgo_on) {
-      T.sor_kernel = CFD_SOR_MULTIGRID;
-      solve_mg_open(out);
-      return;
-    }
-    if (mg_on) {
+    if (mg_method != CFD_POISSON_SOR) {
       T.sor_kernel = CFD_SOR_MULTIGRID;
       solve_mg(out);
       return;
