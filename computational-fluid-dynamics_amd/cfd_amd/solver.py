@@ -55,7 +55,8 @@ class _SolverBase:
         poisson: "sor" (the reference's solve, the default) or "multigrid" (V-cycles to
         the reference's tolerance: the cavity and Rayleigh-Benard on one strip, no ranks;
         see set_poisson_method) or "multigrid-open" (the channel's multigrid solve, one
-        strip, no ranks) or "multigrid-step" (the backwards-facing step's, likewise).
+        strip, no ranks) or "multigrid-step" (the backwards-facing step's, likewise) or
+        "multigrid-any" (the cavity and Rayleigh-Benard at any grid size, likewise).
         mg_options: pre_sweeps / post_sweeps / max_cycles."""
         self.params = params if params is not None else make_params(self.CASE)
         if self.params.case_id != self.CASE:
@@ -97,7 +98,10 @@ class _SolverBase:
         "multigrid-step" is the backwards-facing step's (the channel's scheme over the fluid
         cells, the block's corner coupling part of the operator; every other case and a
         block under 2 cells wide or high, or an inlet under 2 cells high, are refused;
-        plans: mg_step_plan)."""
+        plans: mg_step_plan). "multigrid-any" is the cavity's and Rayleigh-Benard's at any
+        grid whose smaller side is at least 8 (sizes halved rounding up, the last cell of a
+        level as wide as what is left up to the wall; where "multigrid" has the same plan,
+        its bits; the channel and the step are refused; plans: mg_any_plan)."""
         if method not in _lib.POISSON:
             raise ValueError(f"poisson must be one of {sorted(_lib.POISSON)}, got {method!r}")
         opt = mg_options or {}
@@ -235,7 +239,7 @@ class _SolverBase:
         for k in range(1, total + 1):
             t = k * p.dt
             it, res = self.step()
-            cap = self._mg_max_cycles if self.poisson in ("multigrid", "multigrid-open", "multigrid-step") else p.max_iters  # (cycles in the iteration column)
+            cap = self._mg_max_cycles if self.poisson != "sor" else p.max_iters  # (cycles in the iteration column)
             if it >= cap:
                 print(warning_line(p.case_id, cap, res), file=err)
             if k % p.print_interval == 0 or k == total:
@@ -340,6 +344,21 @@ def mg_step_plan(params: CaseParams) -> list[tuple[int, int]]:
     """cfd_mg_step_plan (host only): [(nx, ny)] of every level of the backwards-facing step's
     multigrid plan of these parameters; raises CfdError naming the rule where there is none."""
     return _mg_level_sizes("cfd_mg_step_plan", params)
+
+
+def mg_any_plan(params: CaseParams) -> list[tuple[int, int]]:
+    """cfd_mg_any_plan (host only): [(nx, ny)] of every level of the any-size multigrid plan
+    of these parameters; raises CfdError naming the rule where there is none."""
+    return _mg_level_sizes("cfd_mg_any_plan", params)
+
+
+def mg_any_level(params: CaseParams, level: int) -> list[float]:
+    """cfd_mg_any_level (host only): every constant of one level of the any-size plan, in
+    the order include/cfd_amd.h lists."""
+    cp = to_cparams(params)
+    out = (ctypes.c_double * 72)()
+    _lib.check(_lib.lib().cfd_mg_any_level(ctypes.byref(cp), level, out, 72), "cfd_mg_any_level")
+    return list(out)
 
 
 def params_from_library_rb(ra: float, pr: float, nx: int = 0, ny: int = 0, dt: float = 0.0) -> _lib.CfdParams:

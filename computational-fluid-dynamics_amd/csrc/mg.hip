@@ -18,9 +18,10 @@
 // Every kernel is one template over a scheme: a struct of static per-cell
 // functions over its level type (mg.hpp) - the update of a cell, the coarse
 // source of a coarse cell, the correction of a fine cell, whether a cell is an
-// unknown. The file states the three schemes' cell functions first (the
-// cavity's mg_*, the channel's mgo_*, the step's mgs_*, each in the operand
-// order of its restatement under tests/), then the kernels, then the launches.
+// unknown. The file states the four schemes' cell functions first (the
+// cavity's mg_*, the channel's mgo_*, the step's mgs_*, the any-size cavity's
+// mga_*, each in the operand order of its restatement under tests/), then the
+// kernels, then the launches.
 // What only the step needs - the fluid tests and the coupled pair A / B - sits
 // behind `if constexpr (S::has_pair)` or folds away with S::unknown.
 // The library builds with -ffp-contract=off: no fused multiply-adds.
@@ -399,10 +400,141 @@ struct MgStep {
   }
 };
 
+// =================================================== the cavity, any size ==
+// The fourth scheme (mg.hpp "the cavity at any size", tests/mg_any_reference.py):
+// the cavity's operator with the coefficients of the face between a direction's
+// last two cells, and the transfers' weights at a direction's end. A cell whose
+// stencil touches no such face takes the cavity's expressions (a coefficient of
+// 1 is not multiplied with: the same bits); a coarse cell or a fine cell that
+// takes none of the weights takes the cavity's transfer.
+
+__device__ __forceinline__ bool mga_plain(const MgaLevel* L, int j, int i) {
+  return i > 1 && i < L->x.lim && j > 1 && j < L->y.lim;
+}
+
+__device__ __forceinline__ MgCoef mga_coef(const MgaLevel* L, int j, int i) {
+  MgCoef k;
+  const int cx = i == 1 ? 0 : i == L->nx ? 3 : i == L->nx - 1 ? 2 : 1;
+  const int cy = j == 1 ? 0 : j == L->ny ? 3 : j == L->ny - 1 ? 2 : 1;
+  k.ew = cx == 0 ? 0.0 : cx == 3 ? L->x.c_hi : 1.0;
+  k.ee = cx == 3 ? 0.0 : cx == 2 ? L->x.c_lo : 1.0;
+  k.cs = cy == 0 ? L->cS : cy == 3 ? L->y.c_hi : 1.0;
+  k.en = cy == 3 ? 0.0 : cy == 2 ? L->y.c_lo : 1.0;
+  k.idx = cx | cy << 2;
+  return k;
+}
+
+__device__ __forceinline__ double mga_relax(const MgaLevel* L, int j, int i, double pW, double pE, double pS, double pN,
+                                            double f) {
+  if (mga_plain(L, j, i)) return L->rdiag[5] * (((pE + pW) + (pN + pS)) - f * L->h2);
+  const MgCoef k = mga_coef(L, j, i);
+  return L->rdiag[k.idx] * (((k.ee * pE + k.ew * pW) + (k.en * pN + k.cs * pS)) - f * L->h2);
+}
+
+__device__ __forceinline__ double mga_sor(const MgaLevel* L, int j, int i, double pc, double pW, double pE, double pS,
+                                          double pN, double f) {
+  const MgCoef k = mga_coef(L, j, i);
+  return pc * L->one_m_omega + L->omr[k.idx] * (((k.ee * pE + k.ew * pW) + (k.en * pN + k.cs * pS)) - f * L->h2);
+}
+
+__device__ __forceinline__ double mga_resid(const MgaLevel* L, int j, int i, double c, double pW, double pE, double pS,
+                                            double pN, double f) {
+  if (mga_plain(L, j, i)) return L->ih2 * ((((pE - c) + (pW - c)) + (pN - c)) + (pS - c)) - f;
+  const MgCoef k = mga_coef(L, j, i);
+  return L->ih2 * (((k.ee * (pE - c) + k.ew * (pW - c)) + k.en * (pN - c)) + k.cs * (pS - c)) - f;
+}
+
+// residual of fine cell (j, i), 1 <= j <= ny and 1 <= i <= nx, from fields with rows of P doubles
+__device__ __forceinline__ double mga_resid_at(const MgaLevel* Lf, const double* p, const double* f, size_t P, int j,
+                                               int i) {
+  const size_t o = (size_t)j * P + i;
+  return mga_resid(Lf, j, i, p[o], p[o - 1], p[o + 1], p[o - P], p[o + P], f[o]);
+}
+
+// Coarse source of a cell in the last coarse column of an irregular x and / or the last coarse row of an
+// irregular y: -(b0 hS + b1 hN), hS = a0 rSW + a1 rSE and hN alike; a direction's single child stands alone.
+// Only children inside the grid are read.
+__device__ __forceinline__ double mga_restrict_edge(const MgaLevel* Lf, const double* p, const double* f, size_t P, int J,
+                                                    int I, bool lx, bool ly) {
+  const int j = 2 * J - 1, i = 2 * I - 1;
+  const bool sx = lx && Lf->x.single, sy = ly && Lf->y.single;
+  const double a0 = lx ? Lf->x.r0 : 0.5, a1 = lx ? Lf->x.r1 : 0.5;
+  const double b0 = ly ? Lf->y.r0 : 0.5, b1 = ly ? Lf->y.r1 : 0.5;
+  double hS = mga_resid_at(Lf, p, f, P, j, i);
+  if (!sx) hS = a0 * hS + a1 * mga_resid_at(Lf, p, f, P, j, i + 1);
+  if (sy) return -hS;
+  double hN = mga_resid_at(Lf, p, f, P, j + 1, i);
+  if (!sx) hN = a0 * hN + a1 * mga_resid_at(Lf, p, f, P, j + 1, i + 1);
+  return -(b0 * hS + b1 * hN);
+}
+
+// correction of fine cell (j, i): the cavity's, but where i >= x.first or j >= y.first:
+// ay (ax c + bx H) + by (ax V + bx D) with the directions' weights (3/4, 1/4 in a regular one); b = 0 drops its terms
+__device__ __forceinline__ double mga_corr(const MgaLevel* L, const double* e, int pitch, int j, int i) {
+  const MgLevel* Lc = L + 1;
+  const int kx = i - L->x.first, ky = j - L->y.first;
+  if (kx < 0 && ky < 0) return mg_corr(Lc, e, pitch, j, i);
+  const double ax = kx < 0 ? 0.75 : L->x.pa[kx], bx = kx < 0 ? 0.25 : L->x.pb[kx];
+  const double ay = ky < 0 ? 0.75 : L->y.pa[ky], by = ky < 0 ? 0.25 : L->y.pb[ky];
+  const int J = (j + 1) >> 1, I = (i + 1) >> 1;
+  const int dj = (j & 1) ? -1 : 1, di = (i & 1) ? -1 : 1;
+  double rc = e[(size_t)J * pitch + I];
+  if (bx != 0.0) rc = ax * rc + bx * mg_ext(Lc, e, pitch, J, I + di);
+  if (by == 0.0) return rc;
+  double rv = mg_ext(Lc, e, pitch, J + dj, I);
+  if (bx != 0.0) rv = ax * rv + bx * mg_ext(Lc, e, pitch, J + dj, I + di);
+  return ay * rc + by * rv;
+}
+
+struct MgAny {
+  using Level = MgaLevel;
+  static constexpr bool has_pair = false;
+  static constexpr bool pair_loads = true;
+  static __device__ __forceinline__ bool unknown(const Level*, int, int) { return true; }
+  static __device__ __forceinline__ double relax(const Level* L, int j, int i, double pW, double pE, double pS, double pN,
+                                                 double f) {
+    return mga_relax(L, j, i, pW, pE, pS, pN, f);
+  }
+  static __device__ __forceinline__ double update(const Level* L, const double* p, int P, int j, int i, double f, bool sor) {
+    return sor ? mga_sor(L, j, i, p[0], p[-1], p[1], p[-P], p[P], f) : mga_relax(L, j, i, p[-1], p[1], p[-P], p[P], f);
+  }
+  // An edge cell (above) reads its children cell by cell; every other coarse cell has four children inside
+  // the grid and is the cavity's: the 4 x 4 block p(2J-2 .. 2J+1, 2I-2 .. 2I+1), 2I+1 <= nx+1 and 2J+1 <= ny+1.
+  template <bool Aligned>
+  static __device__ __forceinline__ double coarse_source(const Level* Lf, const double* p, const double* f, size_t P, int J,
+                                                         int I) {
+    const bool lx = I == Lf->x.last, ly = J == Lf->y.last;
+    if (lx || ly) return mga_restrict_edge(Lf, p, f, P, J, I, lx, ly);
+    const size_t o = (size_t)(2 * J - 2) * P + (size_t)(2 * I - 2);
+    double a[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if constexpr (Aligned) {
+        const double2 lo = *reinterpret_cast<const double2*>(p + o + r * P);
+        const double2 hi = *reinterpret_cast<const double2*>(p + o + r * P + 2);
+        a[r][0] = lo.x, a[r][1] = lo.y, a[r][2] = hi.x, a[r][3] = hi.y;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[r][c] = p[o + r * P + c];
+      }
+    }
+    const int j = 2 * J - 1, i = 2 * I - 1;
+    const double rSW = mga_resid(Lf, j, i, a[1][1], a[1][0], a[1][2], a[0][1], a[2][1], f[o + P + 1]);
+    const double rSE = mga_resid(Lf, j, i + 1, a[1][2], a[1][1], a[1][3], a[0][2], a[2][2], f[o + P + 2]);
+    const double rNW = mga_resid(Lf, j + 1, i, a[2][1], a[2][0], a[2][2], a[1][1], a[3][1], f[o + 2 * P + 1]);
+    const double rNE = mga_resid(Lf, j + 1, i + 1, a[2][2], a[2][1], a[2][3], a[1][2], a[3][2], f[o + 2 * P + 2]);
+    return -0.25 * ((rSW + rSE) + (rNW + rNE));
+  }
+  static __device__ __forceinline__ double corr(const Level* L, const double* e, int pitch, int j, int i) {
+    return mga_corr(L, e, pitch, j, i);
+  }
+};
+
 template <class Level> struct MgSchemeOf;
 template <> struct MgSchemeOf<MgLevel> { using type = MgCavity; };
 template <> struct MgSchemeOf<MgoLevel> { using type = MgChannel; };
 template <> struct MgSchemeOf<MgsLevel> { using type = MgStep; };
+template <> struct MgSchemeOf<MgaLevel> { using type = MgAny; };
 
 // ============================================================ the kernels ==
 
@@ -771,6 +903,7 @@ void mg_tail_launch(const Level* dlv, int l0, int last, int nu1, int nu2, const 
 MG_INSTANTIATE(MgLevel)
 MG_INSTANTIATE(MgoLevel)
 MG_INSTANTIATE(MgsLevel)
+MG_INSTANTIATE(MgaLevel)
 #undef MG_INSTANTIATE
 
 void mgs_refresh_launch(const MgsLevel& L, double* cur, const double* prev, const double* own, void* stream) {

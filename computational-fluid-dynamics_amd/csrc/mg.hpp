@@ -2,11 +2,12 @@
 // plans (host only, params.cpp) and the launches of mg.hip. No HIP types here,
 // so host-only code may include it (streams travel as void*, like comm.hip's).
 //
-// One set of kernels and one cycle serve three schemes, each an operator with
+// One set of kernels and one cycle serve four schemes, each an operator with
 // its level type and its plan:
 //   the cavity and Rayleigh-Benard (CFD_POISSON_MULTIGRID, MgLevel),
 //   the channel (CFD_POISSON_MULTIGRID_OPEN, MgoLevel),
-//   the backwards-facing step (CFD_POISSON_MULTIGRID_STEP, MgsLevel).
+//   the backwards-facing step (CFD_POISSON_MULTIGRID_STEP, MgsLevel),
+//   the cavity and Rayleigh-Benard at any grid size (CFD_POISSON_MULTIGRID_ANY, MgaLevel).
 // A V(nu1, nu2) cycle: red-black Gauss-Seidel sweeps, residual + restriction
 // (the residual never reaches memory), the coarsest level by a fixed number of
 // SOR sweeps in one workgroup, the prolongation added to p. Every constant is
@@ -94,6 +95,36 @@ struct MgsLevel : MgoLevel {
   double omrA, omrB; // omega_c * rdA, omega_c * rdB
 };
 
+// The cavity at any size: MgLevel's operator with sizes halved
+// rounding up, n_{l+1} = ceil(n_l / 2). In units of the finest spacing, cells
+// 1 .. n - 1 of level l are W = 2^l wide and cell n is w = n_0 - (n - 1) W
+// (1 <= w <= W): the walls stay where level 0 has them. The operator is the
+// finite-volume one in units of ih2: every coefficient 1 (row 1's south cS) but
+// across the face between cells n - 1 and n, whose centres are (W + w) / 2
+// apart. The restriction is minus the volume-weighted mean of the children's
+// residuals, the prolongation linear between the two nearest coarse centres and
+// constant beyond the last. A direction with w = W, and an even n where a next
+// level follows, is regular: its cells use MgLevel's expressions, so a grid
+// whose MgLevel plan ends on a smaller side below 8 gives that plan's bits.
+// rdiag = 1 / (((ew + ee) + en) + cs), index cx | cy << 2 with a direction's
+// class 0 (cell 1), 1 (2 .. n - 2), 2 (n - 1), 3 (n); every level has n >= 4.
+// tests/mg_any_reference.py states every operation.
+struct MgaDir {
+  int lim;           // cells 2 .. lim - 1 have unit coefficients on both sides: n (w = W) or n - 1
+  int last;          // the next level's cell that takes r0 / r1 (its last one), 0: its cells are all regular
+  int single;        // that cell has one child (n odd)
+  int first;         // cells first .. n take the prolongation weights below (n + 1: none)
+  double c_lo;       // east / north coefficient of cell n - 1: 2 W / (W + w)
+  double c_hi;       // west / south coefficient of cell n: c_lo W / w
+  double r0, r1;     // restriction weights of the last coarse cell's two children: W / (W + w), w / (W + w)
+  double pa[3];      // weight of a fine cell's own coarse cell, cells first, first + 1, first + 2
+  double pb[3];      // ... of the coarse neighbour on the child's side (0: that term is dropped)
+};
+
+struct MgaLevel : MgLevel {
+  MgaDir x, y;
+};
+
 template <class Level>
 struct MgPlanOf {
   int levels = 0;
@@ -103,14 +134,16 @@ struct MgPlanOf {
 using MgPlan = MgPlanOf<MgLevel>;
 using MgoPlan = MgPlanOf<MgoLevel>;
 using MgsPlan = MgPlanOf<MgsLevel>;
+using MgaPlan = MgPlanOf<MgaLevel>;
 
 // The plan of a parameter block, or false with the rule that refused it in
 // `why` (host only: params.cpp).
 bool mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why);
 bool mgo_make_plan(const cfd_params& p, MgoPlan& plan, std::string& why);
 bool mgs_make_plan(const cfd_params& p, MgsPlan& plan, std::string& why);
+bool mga_make_plan(const cfd_params& p, MgaPlan& plan, std::string& why);
 
-// Launches (mg.hip), instantiated for the three level types. dlv: the plan's
+// Launches (mg.hip), instantiated for the four level types. dlv: the plan's
 // levels in device memory; L: the host copy of the level that sizes the grid.
 // One colour of a red-black Gauss-Seidel sweep of level l, in place.
 template <class Level>

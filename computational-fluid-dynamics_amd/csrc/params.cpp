@@ -472,3 +472,117 @@ bool cfd::mgs_make_plan(const cfd_params& p, MgsPlan& plan, std::string& why) {
 extern "C" int cfd_mg_step_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny) {
   return mg_report_levels<cfd::MgsPlan>(p, cfd::mgs_make_plan, levels, level_nx, level_ny);
 }
+
+// The cavity's plan at any size: n_{l+1} = ceil(n_l / 2) while the smaller size is at
+// least 8; a direction's constants as tests/mg_any_reference.py (Direction) forms them.
+namespace {
+
+void mga_direction(MgaDir& D, int l, int n0, int n, bool has_next) {
+  const double W = std::ldexp(1.0, l), w = (double)(n0 - (long long)(n - 1) * (1LL << l));
+  const bool irregular = w != W;
+  D.lim = irregular ? n - 1 : n;
+  D.c_lo = (2.0 * W) / (W + w);
+  D.c_hi = D.c_lo * (W / w);
+  const int nc = (n + 1) / 2;
+  D.single = n % 2 == 1;
+  D.last = 0;
+  D.first = n + 1;
+  D.r0 = D.r1 = 0.5;
+  for (int k = 0; k < 3; ++k) D.pa[k] = 0.75, D.pb[k] = 0.25;
+  if (!(has_next && (D.single || irregular))) return;
+  D.last = nc;
+  D.first = 2 * nc - 2;
+  const double wc = (double)(n0 - (long long)(nc - 1) * (1LL << (l + 1)));
+  if (!D.single) {
+    D.r0 = W / (W + w);
+    D.r1 = w / (W + w);
+  }
+  const double dist = W + 0.5 * wc;  // between the last two coarse centres
+  D.pb[0] = (0.5 * W) / dist;
+  D.pa[0] = 1.0 - D.pb[0];
+  if (D.single) {
+    D.pa[1] = 1.0, D.pb[1] = 0.0;
+  } else {
+    D.pb[1] = (0.5 * w) / dist;
+    D.pa[1] = 1.0 - D.pb[1];
+  }
+  D.pa[2] = 1.0, D.pb[2] = 0.0;  // (n even: cell n lies beyond the last coarse centre)
+}
+
+}  // namespace
+
+bool cfd::mga_make_plan(const cfd_params& p, MgaPlan& plan, std::string& why) {
+  if (p.case_id != CFD_CAVITY && p.case_id != CFD_RAYLEIGH_BENARD) {
+    why = "any-size multigrid covers the cavity and Rayleigh-Benard (case rule): the channel has "
+          "CFD_POISSON_MULTIGRID_OPEN, the step CFD_POISSON_MULTIGRID_STEP";
+    return false;
+  }
+  if (p.nx < 2 || p.ny < 2 || !(p.dx > 0)) {
+    why = "any-size multigrid needs a grid of at least 2 x 2 cells and dx > 0 (grid rule)";
+    return false;
+  }
+  const std::string head = mg_grid_name(p) + " has no any-size multigrid plan (grid rule): ";
+  int sx[MG_MAX_LEVELS], sy[MG_MAX_LEVELS], n = 0;
+  for (int nx = p.nx, ny = p.ny;; nx = (nx + 1) / 2, ny = (ny + 1) / 2) {
+    if (n == MG_MAX_LEVELS) {
+      why = head + "more than " + std::to_string(MG_MAX_LEVELS) + " levels";
+      return false;
+    }
+    sx[n] = nx, sy[n] = ny, ++n;
+    if (std::min(nx, ny) < 8) break;
+  }
+  plan = MgaPlan{};
+  for (int l = 0; l < n; ++l) {
+    MgaLevel& L = plan.lv[l];
+    const double omega = mg_level_base(L, sx[l], sy[l]);
+    L.h2 = std::ldexp(1.0, 2 * l) * (p.dx * p.dx);
+    L.ih2 = 1.0 / L.h2;
+    const double d = 0.5 + std::ldexp(1.0, -(l + 1));
+    L.cS = 1.0 / d;
+    L.g = 1.0 - L.cS;
+    mga_direction(L.x, l, p.nx, sx[l], l + 1 < n);
+    mga_direction(L.y, l, p.ny, sy[l], l + 1 < n);
+    if (n < 2) break;  // (refused below; a level under 4 cells has no four classes)
+    const double ew[4] = {0.0, 1.0, 1.0, L.x.c_hi}, ee[4] = {1.0, 1.0, L.x.c_lo, 0.0};
+    const double cs[4] = {L.cS, 1.0, 1.0, L.y.c_hi}, en[4] = {1.0, 1.0, L.y.c_lo, 0.0};
+    for (int k = 0; k < 16; ++k) {
+      L.rdiag[k] = 1.0 / (((ew[k & 3] + ee[k & 3]) + en[k >> 2]) + cs[k >> 2]);
+      L.omr[k] = omega * L.rdiag[k];
+    }
+  }
+  return mg_finish_plan(plan, n, head, "a second level needs the smaller size at least 8", why);
+}
+
+extern "C" int cfd_mg_any_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny) {
+  return mg_report_levels<cfd::MgaPlan>(p, cfd::mga_make_plan, levels, level_nx, level_ny);
+}
+
+extern "C" int cfd_mg_any_level(const cfd_params* p, int level, double* out, int cap) {
+  if (!p || !out) {
+    cfd::set_last_error("null argument");
+    return CFD_E_ARG;
+  }
+  cfd::MgaPlan plan;
+  std::string why;
+  if (!cfd::mga_make_plan(*p, plan, why)) {
+    cfd::set_last_error(why);
+    return CFD_E_ARG;
+  }
+  if (level < 0 || level >= plan.levels || cap < CFD_MG_ANY_LEVEL_DOUBLES) {
+    cfd::set_last_error("cfd_mg_any_level: no such level, or fewer than CFD_MG_ANY_LEVEL_DOUBLES doubles");
+    return CFD_E_ARG;
+  }
+  const cfd::MgaLevel& L = plan.lv[level];
+  int n = 0;
+  auto put = [&](double v) { out[n++] = v; };
+  put(L.nx), put(L.ny), put(L.pitch), put(L.lds_p), put(L.lds_f), put(L.coarse_sweeps), put(plan.tail);
+  put(L.g), put(L.one_m_omega), put(L.h2), put(L.ih2), put(L.cS);
+  for (double v : L.rdiag) put(v);
+  for (double v : L.omr) put(v);
+  for (const cfd::MgaDir* D : {&L.x, &L.y}) {
+    put(D->lim), put(D->last), put(D->single), put(D->first), put(D->c_lo), put(D->c_hi), put(D->r0), put(D->r1);
+    for (double v : D->pa) put(v);
+    for (double v : D->pb) put(v);
+  }
+  return n == CFD_MG_ANY_LEVEL_DOUBLES ? CFD_OK : CFD_E_STATE;
+}

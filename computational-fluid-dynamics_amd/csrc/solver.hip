@@ -1689,11 +1689,12 @@ class Solver {
   }
 
   // ---------------------------------------------------------- multigrid --
-  // The opt-in multigrid solve (mg.hpp): cfd_set_poisson_method. One driver serves the three
-  // schemes (the cavity's, the channel's, the step's): the launches are mg.hip's templates over the plan's
-  // level type, and what a solve does differently by scheme is in the three hooks solve_mg hands to mg_solve.
+  // The opt-in multigrid solve (mg.hpp): cfd_set_poisson_method. One driver serves the four
+  // schemes (the cavity's, the channel's, the step's, the any-size cavity's): the launches are mg.hip's
+  // templates over the plan's level type, and what a solve does differently by scheme is in the three hooks
+  // solve_mg hands to mg_solve.
   int mg_method = CFD_POISSON_SOR;                 // the active method (SOR: none of the state below)
-  std::variant<MgPlan, MgoPlan, MgsPlan> mg_plan;  // its plan: the alternative mg_method names
+  std::variant<MgPlan, MgoPlan, MgsPlan, MgaPlan> mg_plan;  // its plan: the alternative mg_method names
   void* mg_dlv = nullptr;                          // the plan's levels in device memory
   std::vector<double*> mg_p, mg_f;      // levels >= 1: correction and source, rows 0 .. ny+1 of lv.pitch doubles
   // Fused smoothing (mg_smooth_tile_kernel) writes to a second buffer: mg_q[l] for the multi-launch levels
@@ -1736,7 +1737,8 @@ class Solver {
       mgi.levels = mgi.coarse_nx = mgi.coarse_ny = mgi.coarse_sweeps = 0;
       return;
     }
-    if (method != CFD_POISSON_MULTIGRID && method != CFD_POISSON_MULTIGRID_OPEN && method != CFD_POISSON_MULTIGRID_STEP)
+    if (method != CFD_POISSON_MULTIGRID && method != CFD_POISSON_MULTIGRID_OPEN && method != CFD_POISSON_MULTIGRID_STEP &&
+        method != CFD_POISSON_MULTIGRID_ANY)
       throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
     if (S.size() != 1) throw Error(CFD_E_ARG, "multigrid runs on one strip (strip rule): this solver has n_strips > 1");
     if (comm) throw Error(CFD_E_ARG, "multigrid runs without ranks (rank rule): this is a rank solver");
@@ -1746,6 +1748,7 @@ class Solver {
       throw Error(CFD_E_ARG, "multigrid options: sweeps must be >= 0 with at least one per cycle, max_cycles >= 1");
     if (method == CFD_POISSON_MULTIGRID_STEP) mg_install<MgsPlan>(method, mgs_make_plan);
     else if (method == CFD_POISSON_MULTIGRID_OPEN) mg_install<MgoPlan>(method, mgo_make_plan);
+    else if (method == CFD_POISSON_MULTIGRID_ANY) mg_install<MgaPlan>(method, mga_make_plan);
     else mg_install<MgPlan>(method, mg_make_plan);
     mg_nu1 = nu1;
     mg_nu2 = nu2;
@@ -1927,22 +1930,27 @@ class Solver {
   void solve_mg(cfd_step_info* out) {
     Strip& s = S[0];
     auto warm = [](double*, double tol) { return tol + 1.0; };  // channel-01.cpp:650, backwards_step-01.cpp:890
-    if (mg_method == CFD_POISSON_MULTIGRID) {
+    if (mg_method == CFD_POISSON_MULTIGRID || mg_method == CFD_POISSON_MULTIGRID_ANY) {
       // cavity-01.cpp:610-618: each solve starts from a zero field, ghosts included, and res = 1; after a cycle
-      // the reference's max-norm residual (659-677, final_residual's pass); the whole field is copied back
-      mg_solve(
-          std::get<MgPlan>(mg_plan), out,
-          [&](double* X, double) {
-            HIPC(hipMemsetAsync(X, 0, (size_t)s.g.nrows * pitch * sizeof(double), st));
-            return 1.0;
-          },
-          [&](double* buf, long long& launches) {
-            launches += 1;
-            return mg_resmax([&] { cavity_resmax_kernel<<<pair_grid(s), 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax); });
-          },
-          [&](double* p0, const double* q) {
-            HIPC(hipMemcpyAsync(p0, q, (size_t)(P.ny + 2) * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
-          });
+      // the reference's max-norm residual (659-677, final_residual's pass); the whole field is copied back.
+      // The any-size method's level 0 is the same operator: the same three hooks around its own plan.
+      auto cavity = [&](const auto& plan) {
+        mg_solve(
+            plan, out,
+            [&](double* X, double) {
+              HIPC(hipMemsetAsync(X, 0, (size_t)s.g.nrows * pitch * sizeof(double), st));
+              return 1.0;
+            },
+            [&](double* buf, long long& launches) {
+              launches += 1;
+              return mg_resmax([&] { cavity_resmax_kernel<<<pair_grid(s), 256, 0, st>>>(s.g, C, buf, s.b[B_F], resmax); });
+            },
+            [&](double* p0, const double* q) {
+              HIPC(hipMemcpyAsync(p0, q, (size_t)(P.ny + 2) * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
+            });
+      };
+      if (mg_method == CFD_POISSON_MULTIGRID) cavity(std::get<MgPlan>(mg_plan));
+      else cavity(std::get<MgaPlan>(mg_plan));
     } else if (mg_method == CFD_POISSON_MULTIGRID_OPEN) {
       // channel-01.cpp:642-688 with a V-cycle for the sweep: a warm start from the field the solver holds; after
       // a cycle the reference's ghost refresh (531-541: west and east columns, then south and north rows) and its

@@ -175,14 +175,15 @@ enum cfd_sor_kernel {
  * are even and the smaller is >= 8. Valid with at least two levels and a coarsest level of at most
  * 4096 cells (it is solved in one workgroup's LDS). cfd_mg_plan and cfd_set_poisson_method return
  * CFD_E_ARG, cfd_last_error naming the rule, for the channel and the step (case rule), a grid
- * without a valid plan such as the reference's 63^2 (grid rule), more than one strip (strip rule)
- * and rank solvers (rank rule).
+ * without a valid plan such as the reference's 63^2 (grid rule; CFD_POISSON_MULTIGRID_ANY below takes
+ * such grids), more than one strip (strip rule) and rank solvers (rank rule).
  */
 enum cfd_poisson_method {
   CFD_POISSON_SOR = 0,
   CFD_POISSON_MULTIGRID = 1,      /* the cavity and Rayleigh-Benard */
   CFD_POISSON_MULTIGRID_OPEN = 2, /* the channel (below; added within ABI 14) */
-  CFD_POISSON_MULTIGRID_STEP = 3  /* the backwards-facing step (below; added within ABI 14) */
+  CFD_POISSON_MULTIGRID_STEP = 3, /* the backwards-facing step (below; added within ABI 14) */
+  CFD_POISSON_MULTIGRID_ANY = 4   /* the cavity and Rayleigh-Benard at any grid size (below; added within ABI 14) */
 };
 typedef struct cfd_mg_options {
   int pre_sweeps, post_sweeps, max_cycles;  /* 0 (or a NULL options pointer): 2, 2, 50 */
@@ -212,7 +213,8 @@ int cfd_mg_plan(const cfd_params* p, int* levels, int* coarse_nx, int* coarse_ny
  * and a level whose chosen direction(s) cannot be halved is the coarsest. Coarse levels keep the
  * east zero where the finest grid has it. Valid with 2 .. 16 levels and a coarsest level of at most
  * 4096 cells. Refusals (CFD_E_ARG, cfd_last_error naming the rule): the cavity, Rayleigh-Benard
- * (they have CFD_POISSON_MULTIGRID) and the step (case rule), a grid without a valid plan such as
+ * (they have CFD_POISSON_MULTIGRID and CFD_POISSON_MULTIGRID_ANY) and the step (case rule), a grid
+ * without a valid plan such as
  * the reference's 93 x 31 (grid rule), more than one strip (strip rule), rank solvers (rank rule),
  * bad options.
  *
@@ -236,13 +238,42 @@ int cfd_mg_open_plan(const cfd_params* p, int* levels, int* level_nx, int* level
  * nx is even and >= 8 and the block's width is even and >= 2, y while ny is even and >= 8, the
  * inlet's height is even and >= 2 and the block is at least 2 rows high. Valid with 2 .. 16 levels
  * and a coarsest level of at most 4096 cells. Refusals (CFD_E_ARG, cfd_last_error naming the rule):
- * the other cases (case rule: they have methods 1 and 2), step_i < 2, inlet_jmax < 2 or a block
+ * the other cases (case rule: they have methods 1, 2 and 4), step_i < 2, inlet_jmax < 2 or a block
  * fewer than 2 cells high (geometry rule), a grid without a valid plan such as 472 x 108 (grid
  * rule), more than one strip (strip rule), rank solvers (rank rule), bad options.
  *
  * cfd_mg_step_plan (host only): as cfd_mg_open_plan.
  */
 int cfd_mg_step_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny);
+/*
+ * CFD_POISSON_MULTIGRID_ANY: the cavity's and Rayleigh-Benard's multigrid solve at any grid size
+ * (DESIGN.md §8d), a fourth method beside the other three - same options, same cfd_get_mg_info,
+ * cfd_timing.sor_kernel reports CFD_SOR_MULTIGRID, CFD_POISSON_SOR switches back. New symbols and
+ * one enum value within ABI 14. CFD_POISSON_MULTIGRID, its bits and its refusals are unchanged.
+ *
+ * The solve is CFD_POISSON_MULTIGRID's (zero start, the reference's residual and tolerance) on
+ * levels halved rounding up: n_{l+1} = ceil(n_l / 2) per direction while the smaller size is >= 8.
+ * Cells 1 .. n_l - 1 of level l are 2^l finest cells wide, the last one what is left up to the
+ * wall (1 .. 2^l), so the walls stay where the finest grid has them; the operator is the
+ * finite-volume one on that grid, the restriction the volume-weighted mean over a coarse cell's
+ * children (one child where n_l is odd), the prolongation linear between coarse centres and constant
+ * beyond the last. Where CFD_POISSON_MULTIGRID's plan ends on a smaller size below 8 (64^2, 512^2,
+ * 96 x 64) the plan, the cycle count, the residual and p are that method's, bit for bit. Valid with
+ * 2 .. 16 levels and a coarsest level of at most 4096 cells: the reference's 63^2 and 93 x 31,
+ * 1000^2, 4095^2, 8200^2 all have plans. Refusals (CFD_E_ARG, cfd_last_error naming the rule): the
+ * channel and the step (case rule: they have methods 2 and 3), a smaller size below 8, more than 16
+ * levels or a coarsest level over 4096 cells (grid rule), more than one strip (strip rule), rank
+ * solvers (rank rule), bad options.
+ *
+ * cfd_mg_any_plan (host only): as cfd_mg_open_plan. cfd_mg_any_level (host only) writes every
+ * constant of one level of the plan as doubles, for comparison with tests/mg_any_reference.py: nx,
+ * ny, pitch, lds_p, lds_f, coarse_sweeps, the plan's tail; g, 1 - omega_c, h2, ih2, cS; rdiag[16];
+ * omr[16]; then per direction (x, y) lim, last, single, first, c_lo, c_hi, r0, r1, pa[3], pb[3].
+ * CFD_MG_ANY_LEVEL_DOUBLES doubles in all; `cap` is the room in `out`.
+ */
+#define CFD_MG_ANY_LEVEL_DOUBLES 72
+int cfd_mg_any_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny);
+int cfd_mg_any_level(const cfd_params* p, int level, double* out, int cap);
 
 /* Library / ABI info. */
 int cfd_abi_version(void);

@@ -21,6 +21,9 @@ JSON file per grid under --out.
   python scripts/mg_timing.py --sizes 1024x1024 4096x4096 992x992 --out profiles/mg --commit <hash>
   python scripts/mg_timing.py --case channel --sizes 4096x512 1024x128 --out profiles/mg --commit <hash>
   python scripts/mg_timing.py --case step --sizes 256x32 1024x128 8192x512 --out profiles/mg --commit <hash>
+  python scripts/mg_timing.py --method multigrid-any --sizes 1000x1000 4095x4095 --out profiles/mg --commit <hash>
+
+--method multigrid-any (the cavity at any grid size) writes mg_timing_cavity_any_<size>.json.
 
 The channel's and the step's run fails (exit 1) if a multigrid solve ends above its tolerance.
 """
@@ -93,8 +96,9 @@ def run(cp, steps, warmup, **kw):
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--case", choices=["cavity", "channel", "step"], default="cavity")
-    ap.add_argument("--method", choices=["multigrid", "multigrid-open", "multigrid-step"], default=None,
-                    help="default: multigrid for the cavity, multigrid-open for the channel, multigrid-step for the step")
+    ap.add_argument("--method", choices=["multigrid", "multigrid-open", "multigrid-step", "multigrid-any"], default=None,
+                    help="default: multigrid for the cavity, multigrid-open for the channel, multigrid-step for the step;\n"
+                         "multigrid-any: the cavity at any grid size")
     ap.add_argument("--re", type=float, default=None, help="default: 1000; the step: 400")
     ap.add_argument("--sizes", nargs="+", default=None, help="default: 1024x1024 4096x4096 992x992 (cavity), "
                     "4096x512 1024x128 (channel), 256x32 1024x128 8192x512 (step)")
@@ -128,7 +132,8 @@ def main() -> int:
         if a.case != "cavity" and not (all(v22["converged"]) and all(c22["converged"])):
             ok = False
             print(f"{nx}x{ny}: a multigrid solve ended above its tolerance", file=sys.stderr)
-        path = os.path.join(a.out, f"mg_timing_{a.case}_{nx}x{ny}.json")
+        tag = a.case + ("_any" if method == "multigrid-any" else "")
+        path = os.path.join(a.out, f"mg_timing_{tag}_{nx}x{ny}.json")
         with open(path, "w") as fh:
             json.dump(rec, fh, indent=1)
         d = rec.get("default_sor")
