@@ -86,6 +86,33 @@ class Timing(ctypes.Structure):
                 ("seqsum_serial_chunks", ctypes.c_longlong), ("resident_segments", ctypes.c_longlong)]
 
 
+PLAN_KIND = {0: "pair", 1: "wave", 2: "lexw", 3: "interior"}  # enum cfd_sor_plan_kind
+SOR_PLAN_MAX = 8
+
+
+class SorBandPlan(ctypes.Structure):
+    """cfd_sor_band_plan: one distinct launch plan of a solve."""
+    _fields_ = [(n, ctypes.c_int) for n in (
+        "kind", "sweeps", "proof", "waves", "lo0", "hi0", "lo1", "hi1", "ctiles", "th", "nb0", "nb1", "the", "nbe0",
+        "nbe1", "nl", "ncx", "tiles", "extra", "max_th", "budget_bands", "shortened", "clamped", "march_order",
+        "launch_tiles", "up_bands", "xn", "xbn", "left_tiles")] + [("launches", ctypes.c_longlong)]
+
+
+class SorPlan(ctypes.Structure):
+    """cfd_sor_plan: the launch plans of the most recent pressure solve."""
+    _fields_ = [("sor_kernel", ctypes.c_int), ("n_plans", ctypes.c_int), ("plans_dropped", ctypes.c_int),
+                ("plan", SorBandPlan * SOR_PLAN_MAX),
+                ("ramp_launches", ctypes.c_longlong), ("ramp_th_min", ctypes.c_int), ("ramp_th_max", ctypes.c_int),
+                ("ramp_nb_max", ctypes.c_int), ("ramp_tiles_max", ctypes.c_int), ("ramp_up", ctypes.c_int),
+                ("ramp_by_budget", ctypes.c_longlong), ("ramp_by_floor", ctypes.c_longlong),
+                ("ramp_grown_bands", ctypes.c_longlong), ("ramp_grown_tiles", ctypes.c_longlong),
+                ("ramp_fallback", ctypes.c_longlong)]
+
+    @property
+    def plans(self) -> list[SorBandPlan]:
+        return [self.plan[q] for q in range(self.n_plans)]
+
+
 # every symbol include/cfd_amd.h declares: name -> (restype, argtypes)
 _vp, _i, _d, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -119,6 +146,7 @@ SIGNATURES = {
     "cfd_reset_timing": (_i, [_vp]),
     "cfd_synchronize": (_i, [_vp]),
     "cfd_set_tuning": (_i, [_vp, _i, _i]),
+    "cfd_sor_plan_info": (_i, [_vp, ctypes.POINTER(SorPlan)]),
     "cfd_tuning_default": (_i, [ctypes.POINTER(CfdParams), _i, _ip]),
     "cfd_set_poisson_method": (_i, [_vp, _i, ctypes.POINTER(MgOptions)]),
     "cfd_get_mg_info": (_i, [_vp, ctypes.POINTER(MgInfo)]),

@@ -87,6 +87,13 @@ class _SolverBase:
         """cfd_set_tuning: a launch-planning knob (performance only, same bits)."""
         _lib.check(_lib.lib().cfd_set_tuning(self._h, _lib.TUNING[knob], int(value)), "cfd_set_tuning")
 
+    def sor_plan(self) -> _lib.SorPlan:
+        """cfd_sor_plan_info: the launch plans the most recent pressure solve ran (band plans
+        with their launch counts, the reference order's ramp heights); read only."""
+        rep = _lib.SorPlan()
+        _lib.check(_lib.lib().cfd_sor_plan_info(self._h, ctypes.byref(rep)), "cfd_sor_plan_info")
+        return rep
+
     def set_poisson_method(self, method: str, mg_options: dict[str, int] | None = None) -> None:
         """cfd_set_poisson_method: "multigrid" makes solverPressurePoisson() / step() run
         V(pre_sweeps, post_sweeps) cycles (defaults 2, 2; at most max_cycles, default 50)

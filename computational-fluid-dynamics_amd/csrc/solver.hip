@@ -244,6 +244,49 @@ class Solver {
   int tent_th = 64;            // rows per band of the predictor's march
   int n_cu = 256;              // compute units of the device
 
+  // cfd_sor_plan_info: the plans of the most recent solve, noted where its launches are planned
+  // (launch_poisson, multi_overlapped, launch_lexw). Bookkeeping only: nothing reads it back.
+  // What multi_plan / wave_bands know about a plan beyond the PairPlan itself:
+  struct PlanNote {
+    int waves = 0, sweeps = 0, extra = 0, max_th = 1 << 30, tiles = 0;
+    bool budget_bands = false, shortened = false;
+    int clamped = 0;
+  };
+  cfd_sor_plan rep{};
+  // the entry of a plan in rep.plan (appended at its first launch; nullptr: the table is full)
+  cfd_sor_band_plan* rep_plan(int kind, const PairPlan& pl, const PlanNote& nt, bool proof) {
+    cfd_sor_band_plan b{};
+    b.kind = kind;
+    b.sweeps = nt.sweeps;
+    b.proof = proof ? 1 : 0;
+    b.waves = nt.waves;
+    b.lo0 = pl.lo0; b.hi0 = pl.hi0; b.lo1 = pl.lo1; b.hi1 = pl.hi1;
+    b.ctiles = pl.ctiles;
+    b.th = pl.th; b.nb0 = pl.nb0; b.nb1 = pl.nb1;
+    b.the = pl.the; b.nbe0 = pl.nbe0; b.nbe1 = pl.nbe1;
+    b.nl = pl.nl; b.ncx = pl.ncx;
+    b.tiles = nt.tiles;
+    b.extra = nt.extra;
+    b.max_th = nt.max_th;
+    b.budget_bands = nt.budget_bands;
+    b.shortened = nt.shortened;
+    b.clamped = nt.clamped;
+    b.march_order = kind == CFD_PLAN_LEXW ? 0 : (march_flags >> 3) & 1;
+    for (int q = 0; q < rep.n_plans; ++q) {
+      const cfd_sor_band_plan& a = rep.plan[q];
+      if (a.kind == b.kind && a.sweeps == b.sweeps && a.proof == b.proof && a.waves == b.waves && a.lo0 == b.lo0 &&
+          a.hi0 == b.hi0 && a.lo1 == b.lo1 && a.hi1 == b.hi1 && a.th == b.th && a.the == b.the && a.nb0 == b.nb0 &&
+          a.nbe0 == b.nbe0 && a.tiles == b.tiles && a.march_order == b.march_order)
+        return &rep.plan[q];
+    }
+    if (rep.n_plans == CFD_SOR_PLAN_MAX) {
+      ++rep.plans_dropped;
+      return nullptr;
+    }
+    rep.plan[rep.n_plans] = b;
+    return &rep.plan[rep.n_plans++];
+  }
+
   // cfd_set_tuning (include/cfd_amd.h enum cfd_tuning): launch planning only
   void set_tuning(int knob, int v) {
     set_tuning_value(knob, v);
@@ -838,8 +881,10 @@ class Solver {
   // the step's block (left of its column and across it) become their own
   // class (PairPlan::nl / ncx): interior-path bands below the block, short
   // masked bands next to its lower edge and above it.
+  // note (optional): what cfd_sor_plan_info reports about the plan (written, never read here)
   PairPlan multi_plan(int lo0, int hi0, int lo1, int hi1, int waves, int n, int max_th = 1 << 30,
-                      int edge_pct = -1, int twc = PAIR_TWC, int ex = -1, bool left_class = false) const {
+                      int edge_pct = -1, int twc = PAIR_TWC, int ex = -1, bool left_class = false,
+                      PlanNote* note = nullptr) const {
     if (edge_pct < 0) edge_pct = pair_edge_pct;
     PairPlan pl{};
     pl.ctiles = (P.nx + 2 + twc - 1) / twc;
@@ -886,6 +931,8 @@ class Solver {
     };
     int nb = std::max(1, std::min(waves / std::max(1, pl.ctiles), (rows + march_min_th - 1) / march_min_th));
     nb = std::max(nb, (rows + max_th - 1) / max_th);
+    const int nb_first = nb;
+    bool clamped = false;
     for (;; --nb) {  // most interior bands whose tiles (boundary tiles included) fit one round
       pl.th = std::max(1, std::min(rmax, ((rows + nb - 1) / nb + ex + 9) / 10 * 10 - ex));
       if (pl.th > max_th) {  // (lexw: one wave marches at most max_th rows)
@@ -896,6 +943,7 @@ class Solver {
         pl.nbe0 = nbands(lo0, hi0, pl.the);
         pl.nbe1 = nbands(lo1, hi1, pl.the);
         left_bands();
+        clamped = true;
         break;
       }
       pl.the = std::max(8, std::min(rmax, (pl.th + ex) * edge_pct / 100 - ex));
@@ -905,6 +953,16 @@ class Solver {
       pl.nbe1 = nbands(lo1, hi1, pl.the);
       left_bands();
       if (plan_waves(pl) <= waves || nb == 1) break;
+    }
+    if (note) {
+      note->waves = waves;
+      note->sweeps = n;
+      note->extra = ex;
+      note->max_th = max_th;
+      note->tiles = plan_waves(pl);
+      note->budget_bands = waves / std::max(1, pl.ctiles) < (rows + march_min_th - 1) / march_min_th;
+      note->shortened = nb < nb_first;
+      note->clamped = clamped ? 1 : (pl.th == rmax && ((pl.th + ex) % 10) != 0) ? 2 : 0;
     }
     return pl;
   }
@@ -958,12 +1016,27 @@ class Solver {
       const Geo& g = S[q].g;
       const int rows = g.wj1 - g.wj0 + 1;
       int ctiles, th, nbands;
+      PlanNote nt;
       if (n >= 2) {
         const PairPlan pl = multi_plan(g.wj0, g.wj1 + 1, 0, 0, resident_pair_waves / (int)S.size(), n, 1 << 30, -1,
-                                       PAIR_TWC, -1, open_proof_n(n));
+                                       PAIR_TWC, -1, open_proof_n(n), &nt);
+        if (cfd_sor_band_plan* b = rep_plan(CFD_PLAN_PAIR, pl, nt, proof_launch && !replay)) ++b->launches;
         launch_multi<CASE>(n, pl, g, pin[q], pout[q], S[q].b[B_F], ctl, k, ka, kb, st, replay);
       } else {
         wave_bands(rows, 128 - 8, resident_waves, ctiles, th, nbands);
+        {  // (the report's view of wave_bands: one class of ctiles x nbands tiles)
+          PairPlan pw{};
+          pw.ctiles = ctiles;
+          pw.th = pw.the = th;
+          pw.nb0 = pw.nbe0 = nbands;
+          pw.lo0 = g.wj0; pw.hi0 = g.wj1 + 1;
+          nt.waves = resident_waves / (int)S.size();
+          nt.sweeps = 1;
+          nt.extra = 0;
+          nt.tiles = ctiles * nbands;
+          nt.budget_bands = std::max(1, resident_waves / (ctiles * (int)S.size())) < (rows + march_min_th - 1) / march_min_th;
+          if (cfd_sor_band_plan* b = rep_plan(CFD_PLAN_WAVE, pw, nt, false)) ++b->launches;
+        }
         const int nblk = (ctiles * nbands + 3) / 4;
         poisson_wave_kernel<CASE><<<nblk, 256, 0, st>>>(g, C, pin[q], pout[q], S[q].b[B_F], ctl, k, ka, kb, th, ctiles,
                                                          nbands, march_flags | (replay ? 4 : 0) | (window_proof ? 128 : 0));
@@ -1037,8 +1110,10 @@ class Solver {
     pb.nb1 = pb.nbe1 = hi_b ? 1 : 0;
     launch_multi<CASE>(n, pb, g, pin, pout, s.b[B_F], ctl, k, ka, kb, st_b);
     if (m > 0) HIPC(hipStreamWaitEvent(st, ev_bnd[pe], 0));
+    PlanNote nt;
     const PairPlan pi = multi_plan(g.wj0 + lo_b, g.wj1 + 1 - hi_b, 0, 0, resident_pair_waves - 2 * pb.ctiles, n,
-                                   1 << 30, -1, PAIR_TWC, -1, open_proof_n(n));
+                                   1 << 30, -1, PAIR_TWC, -1, open_proof_n(n), &nt);
+    if (cfd_sor_band_plan* b = rep_plan(CFD_PLAN_INTERIOR, pi, nt, proof_launch)) ++b->launches;
     launch_multi<CASE>(n, pi, g, pin, pout, s.b[B_F], ctl, k, ka, kb, st);
     check_launch("poisson (overlapped)");
     HIPC(hipEventRecord(ev_int[e], st));
@@ -1162,10 +1237,87 @@ class Solver {
       }
   }
 
+  // cfd_sor_plan_info, host only: which marches poisson_lexw_kernel's decode gives the tiles of a
+  // launch - the kernel's own tests restated (lexw.hpp), so that the report says what ran.
+  // An interior band [y0, y1) of a plain open-case column tile is row-checked (never marched up):
+  bool lexw_row_checked(int ns, const Geo& g, int y0, int y1, bool left) const {
+    const int H = 2 * ns + 1;
+    const int rmin = std::max(g.row_lo, 0);
+    int rmax = std::min(g.row_lo + g.nrows - 1, g.ny + 1);
+    const int jg = left ? C.inlet_jmax + 1 : g.ny + 1;
+    if (left) rmax = std::min(rmax, C.inlet_jmax + 2);
+    return CFD_LEXW_ALLRC || !(y0 - H + 1 > rmin && y1 + H + 2 * ns < std::min(rmax, jg));
+  }
+  // a steady launch: the interior column tiles of the step's left class, and the odd interior bands
+  // that march up in the plain interior column tiles (neither left class nor crossing)
+  void lexw_steady_classes(int ns, const PairPlan& pl, const Geo& g, bool updown, int* left_tiles, int* up_bands) const {
+    const int twc = lexw_twc(ns), ch = lexw_ch(ns);
+    int nleft = 0, plain = 0;
+    for (int ct = 1; ct + 1 < pl.ctiles; ++ct) {
+      const int c0 = ct * twc - ch;
+      if (P.case_id != CFD_BACKSTEP) ++plain;
+      else if (c0 + 127 <= C.step_i - 1 && lexw_left_class()) ++nleft;
+      else if (c0 > C.step_i + 1) ++plain;
+    }
+    int up = 0;
+    if (updown && plain > 0)
+      for (int b = 1; b < pl.nb0 + pl.nb1; b += 2) {
+        const bool r0 = b < pl.nb0;
+        const int y0 = r0 ? pl.lo0 + b * pl.th : pl.lo1 + (b - pl.nb0) * pl.th;
+        const int y1 = std::min(y0 + pl.th, r0 ? pl.hi0 : pl.hi1);
+        if (y0 < y1 && (P.case_id == CFD_CAVITY || !lexw_row_checked(ns, g, y0, y1, false))) ++up;
+      }
+    *left_tiles = nleft;
+    *up_bands = up;
+  }
+  // a ramp launch: does some tile take the upward march (an odd band's whole-band interior tile,
+  // wholly active in every half-sweep the launch evaluates, unmasked and unchecked)?
+  bool lexw_ramp_up(int ns, const PairPlan& pl, const Geo& g, const LexRamp& rp,
+                    const std::vector<std::pair<int, int>>& rr, int H0, int K) const {
+    const bool open = P.case_id != CFD_CAVITY;
+    const int H = 2 * ns + 1, twc = lexw_twc(ns), ch = lexw_ch(ns), glo = open ? 0 : 1;
+    const int Hend = H0 + 2 * ns - 1, last = 2 * (K - 1) + (open ? 2 : 0);
+    for (int b = 1; b < rp.nb; b += 2) {
+      const unsigned e = rp.band[b];
+      const int ca = (e >> 8) & 255, cb = e & 255;
+      const bool xsplit = rp.xn > 0 && rp.row0 + (b + 1) * rp.th + rp.xreach >= 0;  // (lexw_ramp_waves: half bands)
+      for (int c = std::max(ca, 1); c <= std::min(cb, pl.ctiles - 2); ++c) {
+        if (xsplit && c >= rp.xa && c < rp.xa + rp.xn) continue;
+        const int y0 = std::max(rp.row0 + b * rp.th, rr[c].first);
+        int y1 = std::min(rp.row0 + (b + 1) * rp.th, rr[c].second + 1);
+        const int c0 = c * twc - ch;
+        bool left = false;
+        if (P.case_id == CFD_BACKSTEP && c0 + 127 <= C.step_i - 1 && lexw_left_class()) {
+          left = c0 >= 1;
+          y1 = std::min(y1, C.inlet_jmax + 2);
+        }
+        if (y0 >= y1) continue;
+        const int rlo = std::max(std::max(y0 - H - 1, glo), g.row_lo);
+        const int rhi = std::min(std::min(y1 + H, g.ny + 1 - glo), g.row_lo + g.nrows - 1);
+        const int clo = std::max(c0, glo), chi = std::min(c0 + 127, g.nx + 1 - glo);
+        const int smin = clo + rlo, smax = chi + rhi;
+        if (smin > Hend || smax + last < H0 - 2 * ns) continue;
+        if (!(open ? (c0 >= 1 && c0 + 127 <= g.nx) : (clo == c0 && chi == c0 + 127))) continue;  // (cols_in)
+        if (!open) {
+          if (smax <= H0 - 2 && Hend <= smin + last) return true;
+          continue;
+        }
+        if (P.case_id == CFD_BACKSTEP && !left) {
+          const int jb = C.inlet_jmax + 1, si = C.step_i;
+          if (c0 + 127 <= si - 1 && y0 - H - 1 >= jb + 1 && y1 + H + 2 * ns + 1 <= g.ny) continue;  // (solids only)
+          if (y1 + H + 2 * ns + 1 >= jb - 1 && c0 <= si + 1) continue;                               // (the general tiles)
+        }
+        if (!lexw_row_checked(ns, g, y0, y1, left) && smax <= H0 - 2 && Hend <= smin + 2 * (K - 1)) return true;
+      }
+    }
+    return false;
+  }
+
   void launch_lexw(int ns, bool steady, bool sample, const PairPlan& pl, const Geo& g, const double* pin,
                    double* pout, const double* f, const LexCtl& L, int H0, int K, int ka, int kb, bool replay,
-                   int waves) {
+                   int waves, const PlanNote& nt) {
     const int fl = (replay ? 4 : 0) | (lexw_left_class() ? 8 : 0) | (lexw_updown ? 16 : 0);
+    cfd_sor_band_plan* const rb = rep_plan(CFD_PLAN_LEXW, pl, nt, false);  // (cfd_sor_plan_info)
     const int ne = pl.ctiles >= 2 ? 2 : 1;
     int ntiles = ne * (pl.nbe0 + pl.nbe1) + (pl.ctiles - ne) * (pl.nb0 + pl.nb1);
     LexRamp rp{};
@@ -1222,13 +1374,36 @@ class Solver {
       };
       int th = (int)std::max<long long>(1, (tot + waves - 1) / std::max(1, waves));
       // (a floor on the band height trades idle wave slots for less pipeline fill per output row)
+      const bool by_floor = pl.th * lexw_ramp_pct / 100 > th;  // (by_floor .. fell_back: cfd_sor_plan_info)
       th = std::max(th, pl.th * lexw_ramp_pct / 100);
       th = std::max(1, (th + ex + 9) / 10 * 10 - ex);
-      while ((rh - rl) / th + 1 > LEXW_RAMP_BANDS) th += 10;
+      bool grown_bands = false, grown_tiles = false, fell_back = false;
+      while ((rh - rl) / th + 1 > LEXW_RAMP_BANDS) {
+        th += 10;
+        grown_bands = true;
+      }
       ntiles = build(th);
-      while (th < pl.th && ntiles > waves) ntiles = build(th += 10);
-      if (th > pl.th) ntiles = build(th = std::max(pl.th, (rh - rl) / LEXW_RAMP_BANDS + 1));
+      while (th < pl.th && ntiles > waves) {
+        ntiles = build(th += 10);
+        grown_tiles = true;
+      }
+      if (th > pl.th) {
+        ntiles = build(th = std::max(pl.th, (rh - rl) / LEXW_RAMP_BANDS + 1));
+        fell_back = true;
+      }
       if (pl.ctiles > 255 || ntiles >= 65536) throw Error(CFD_E_ARG, "lexicographic ordering: grid too wide");
+      if (ntiles > 0) {
+        ++rep.ramp_launches;
+        rep.ramp_th_min = rep.ramp_th_min ? std::min(rep.ramp_th_min, rp.th) : rp.th;
+        rep.ramp_th_max = std::max(rep.ramp_th_max, rp.th);
+        rep.ramp_nb_max = std::max(rep.ramp_nb_max, rp.nb);
+        rep.ramp_tiles_max = std::max(rep.ramp_tiles_max, ntiles);
+        ++(by_floor ? rep.ramp_by_floor : rep.ramp_by_budget);
+        rep.ramp_grown_bands += grown_bands;
+        rep.ramp_grown_tiles += grown_tiles;
+        rep.ramp_fallback += fell_back;
+        if ((fl & 16) && sample && !rep.ramp_up) rep.ramp_up = lexw_ramp_up(ns, pl, g, rp, rr, H0, K) ? 1 : 0;
+      }
     }
     // the step's steady launches: the crossing column tiles' bands that reach
     // the block's edge as CFD_LEXW_XSPLIT shorter bands (lexw.hpp; they set
@@ -1249,6 +1424,13 @@ class Solver {
         plx.xparts = CFD_LEXW_XSPLIT;
         ntiles += plx.xn * plx.xbn * (plx.xparts - 1);
       }
+    }
+    if (steady && rb && ntiles > 0) {  // (cfd_sor_plan_info: what this steady launch runs)
+      ++rb->launches;
+      rb->launch_tiles = ntiles;
+      rb->xn = plx.xn;
+      rb->xbn = plx.xbn;
+      lexw_steady_classes(ns, pl, g, (fl & 16) && sample, &rb->left_tiles, &rb->up_bands);
     }
     if (ntiles == 0) return;
     const dim3 grid((ntiles + 3) / 4);
@@ -1307,12 +1489,13 @@ class Solver {
     // (kexact >= K: no iteration the solve tests is evaluated everywhere)
     const int m_full = (!tests || kexact >= K) ? INT32_MAX : (ns >= 3) ? (2 * kexact - 1) / (2 * ns) : 0;
     std::vector<PairPlan> plans(S.size());
+    std::vector<PlanNote> notes(S.size());
     for (size_t q = 0; q < S.size(); ++q)
       plans[q] = multi_plan(S[q].g.wj0, S[q].g.wj1 + 1, 0, 0, resident_lexw_waves / (int)S.size(), ns,
                             // (a wave's march steps + 9 <= 127: its iterations fit one 64-bit
                             // mask; at 6 sweeps 90 + 2 * 13 + 1 + 9 = 126)
                             ns >= 5 ? 90 : 96,
-                            lexw_edge_pct, lexw_twc(ns), lexw_extra(ns));
+                            lexw_edge_pct, lexw_twc(ns), lexw_extra(ns), false, &notes[q]);
     // steady launches of strip q: every cell the strip's launch touches (its
     // rows and the HALO rows on each side: i + j in [smin, smax]) active in
     // every half-sweep of the launch and of the previous one's last
@@ -1363,7 +1546,7 @@ class Solver {
         if (steady && m == ms0) HIPC(hipEventRecord(ev_f0, st));
         for (size_t q = 0; q < S.size(); ++q)
           launch_lexw(ns, m >= qs0[q] && m <= qs1[q], m < m_full, plans[q], S[q].g, S[q].b[bin], S[q].b[bout],
-                      S[q].b[B_F], L, 2 + 2 * ns * m, K, ka, kb, !tests, resident_lexw_waves / (int)S.size());
+                      S[q].b[B_F], L, 2 + 2 * ns * m, K, ka, kb, !tests, resident_lexw_waves / (int)S.size(), notes[q]);
         check_launch("poisson_lexw");
         if (steady && m == ms1) HIPC(hipEventRecord(ev_f1, st));
       }
@@ -1995,6 +2178,12 @@ class Solver {
   }
 
   void solve(cfd_step_info* out) {
+    rep = cfd_sor_plan{};  // (cfd_sor_plan_info covers this solve)
+    solve_by_engine(out);
+    rep.sor_kernel = T.sor_kernel;
+  }
+
+  void solve_by_engine(cfd_step_info* out) {
     if (mg_method != CFD_POISSON_SOR) {
       T.sor_kernel = CFD_SOR_MULTIGRID;
       solve_mg(out);
@@ -2984,6 +3173,12 @@ int cfd_get_mg_info(cfd_solver* s, cfd_mg_info* out) {
 }
 int cfd_synchronize(cfd_solver* s) { return guard([&] { HIPC(hipStreamSynchronize(S_(s)->st)); }); }
 int cfd_set_tuning(cfd_solver* s, int knob, int value) { return guard([&] { S_(s)->set_tuning(knob, value); }); }
+int cfd_sor_plan_info(cfd_solver* s, cfd_sor_plan* out) {
+  return guard([&] {
+    if (!out) throw Error(CFD_E_ARG, "null output");
+    *out = S_(s)->rep;
+  });
+}
 
 int cfd_owned_rows(const cfd_solver* s, int* first, int* last) {
   return guard([&] {

@@ -356,7 +356,8 @@ enum cfd_tuning {
   CFD_TUNE_MARCH_MIN_TH = 5,  /* minimum rows per band of a march launch (>= 1; default 16 for the channel
                                  and for the reference order, 24 for the red-black cavity / step) */
   CFD_TUNE_TENT_TH = 6,       /* rows per band of the predictor's march (>= 4) */
-  CFD_TUNE_LEXW_RAMP_PCT = 7, /* lexicographic ramp launches: band height floor, % of the steady plan's (0..100) */
+  CFD_TUNE_LEXW_RAMP_PCT = 7, /* lexicographic ramp launches: band height floor, % of the steady plan's (0..100;
+                                 default 0, the backwards step 100) */
   CFD_TUNE_TILE_ROUNDS = 8,   /* red-black, one strip: LDS-tile launches when the grid fits this many
                                  resident rounds of tiles (one per CU; 0: never, the march launches;
                                  default 1 for the cavity, 0 for the open cases) */
@@ -376,6 +377,82 @@ enum cfd_tuning {
                                  time), 0 = every band marches down (ABI 12) */
 };
 int cfd_set_tuning(cfd_solver* s, int knob, int value);
+/*
+ * The launch plans of the most recent pressure solve (host-side bookkeeping, read only: nothing is
+ * launched or planned differently for it). Added within ABI 14: one new symbol and new structs only -
+ * no existing struct, default or function changes. It is what lets a test of the knobs above show
+ * that a value produced the plan shape it was chosen for (tests/test_gpu_tuning.py).
+ *
+ * A band plan tiles rows [lo0, hi0) + [lo1, hi1) of one strip: every interior column tile in bands
+ * of th rows, the first and last column tile (masked marches) in bands of `the` rows, at most `waves`
+ * tiles (one resident round) unless the plan is down to one band or th is clamped. Interior bands are
+ * marched in groups of 10 rows over th + extra rows, so th + extra is a multiple of 10 unless th was
+ * cut to the rows there are or clamped to max_th. A solve runs several plans (proof and exact launches,
+ * a shorter last launch, a replay, one plan per strip): plan[] holds each distinct one once, in the
+ * order first launched, with the number of launches that ran it.
+ */
+enum cfd_sor_plan_kind {
+  CFD_PLAN_PAIR = 0,     /* red-black fused launch of 2 - 4 sweeps (Solver::multi_plan) */
+  CFD_PLAN_WAVE = 1,     /* red-black one-sweep launch (Solver::wave_bands): no boundary class (the = th),
+                            no 10-row groups (extra 0) */
+  CFD_PLAN_LEXW = 2,     /* reference order: the steady plan (multi_plan); the ramp launches tile by their own
+                            heights, reported in cfd_sor_plan */
+  CFD_PLAN_INTERIOR = 3  /* red-black ranks with halo overlap: the interior rows of a fused launch, planned for
+                            the budget less the two boundary launches' tiles (those are fixed 16-row bands and
+                            not reported) */
+};
+#define CFD_SOR_PLAN_MAX 8
+typedef struct cfd_sor_band_plan {
+  int kind;             /* enum cfd_sor_plan_kind */
+  int sweeps;           /* SOR iterations per launch */
+  int proof;            /* red-black: 1 = launched with the proof-mode test */
+  int waves;            /* the wave budget: tiles of one resident round, per strip */
+  int lo0, hi0, lo1, hi1;
+  int ctiles;           /* column tiles */
+  int th, nb0, nb1;     /* interior column tiles: band height, bands in either row range */
+  int the, nbe0, nbe1;  /* boundary column tiles */
+  int nl, ncx;          /* the step's red-black proof launches: column tiles left of / across the step's
+                           column that form their own class (0, 0: none) */
+  int tiles;            /* tiles of the plan, every class: what the planner held against the budget */
+  int extra;            /* rows a wave marches beyond its band */
+  int max_th;           /* most rows one wave may march (reference order: 96, from 5 sweeps on 90; else 1 << 30) */
+  int budget_bands;     /* 1: the first band count came from the budget (waves / ctiles), not from the
+                           CFD_TUNE_MARCH_MIN_TH floor */
+  int shortened;        /* 1: the search loop then lowered the band count until the tiles fit the budget */
+  int clamped;          /* 1: th was clamped to max_th (the search stops there); 2: th was cut to the rows of
+                           the longer range (a band cannot be taller) */
+  int march_order;      /* red-black kinds: CFD_TUNE_MARCH_ORDER as launched */
+  /* reference order, the last steady launch that ran the plan (0 before one): */
+  int launch_tiles;     /* tiles launched (the step's split parts included) */
+  int up_bands;         /* interior bands that march up in the plain interior column tiles (odd bands, with
+                           CFD_TUNE_LEXW_UPDOWN, in sampled launches; the open cases' row-checked first and
+                           last bands stay down) */
+  int xn, xbn;          /* the step: crossing column tiles and the bands of them split into shorter parts */
+  int left_tiles;       /* the step: interior column tiles in the left class (CFD_TUNE_LEXW_LEFT), the wall
+                           tile not counted */
+  long long launches;   /* launches enqueued with the plan, replays included (reference order: the steady
+                           ones); those enqueued past a stop exit at entry, so this may exceed
+                           cfd_timing.poisson_launches */
+} cfd_sor_band_plan;
+typedef struct cfd_sor_plan {
+  int sor_kernel;       /* enum cfd_sor_kernel of the solve (CFD_SOR_NONE before the first) */
+  int n_plans;          /* entries of plan[] in use (0 for the engines that plan no bands) */
+  int plans_dropped;    /* launches whose plan found no room in plan[] (never expected) */
+  cfd_sor_band_plan plan[CFD_SOR_PLAN_MAX];
+  /* Reference order, the ramp launches of the solve (replays and continuations included), summed over
+   * the strips. Heights: the start is ceil(touched rows / waves) (ramp_by_budget) unless
+   * CFD_TUNE_LEXW_RAMP_PCT % of the steady th is larger (ramp_by_floor); rounded up to 10-row groups;
+   * raised by 10 while the bands exceed the 256-entry band table (ramp_grown_bands) and while the tiles
+   * exceed the budget, up to the steady th (ramp_grown_tiles); past the steady th, the steady th or what
+   * 256 bands need (ramp_fallback). A launch counts under one of the first two and under each of the
+   * last three that changed its height. */
+  long long ramp_launches;
+  int ramp_th_min, ramp_th_max;       /* band heights used (0, 0: no ramp launch) */
+  int ramp_nb_max, ramp_tiles_max;    /* most bands (LexRamp::nb) and most tiles of one ramp launch */
+  int ramp_up;                        /* 1: some ramp launch marched a wholly active interior tile up */
+  long long ramp_by_budget, ramp_by_floor, ramp_grown_bands, ramp_grown_tiles, ramp_fallback;
+} cfd_sor_plan;
+int cfd_sor_plan_info(cfd_solver* s, cfd_sor_plan* out);
 /* The default a solver created from these parameters starts with (host only, no
  * device needed; ABI 9). The waves-per-SIMD knobs (PAIR_WPS, WAVE_WPS,
  * LEXW_WAVES) come from the device's occupancy: CFD_E_STATE. */

@@ -37,7 +37,8 @@ def run_ranks(cp, world, steps, check_every=1, timing=False, **kw):
             md, ke = s.statistics()
             results[r] = dict(rows=s.owned_rows(), u=s.field("u"), v=s.field("v"), p=s.field("p"), its=its,
                               stats=(md, ke), overlapped=s.timing().poisson_overlapped,
-                              fallbacks=s.timing().proof_fallbacks)
+                              fallbacks=s.timing().proof_fallbacks, launches=s.timing().poisson_launches,
+                              sweeps=s.timing().poisson_sweeps, plan=s.sor_plan())
             s.close()
             L.cfd_comm_destroy(comm)
         except Exception as e:  # noqa: BLE001
