@@ -35,11 +35,11 @@ def tu_sources(tu: str) -> list[str]:
     if tu == "solver":
         deps = glob.glob(os.path.join(CSRC, "*.hpp"))
     elif tu == "tile":
-        deps = [os.path.join(CSRC, n) for n in ("tile.hpp", "device.hpp")]
+        deps = [os.path.join(CSRC, n) for n in ("tile.hpp", "device.hpp", "plan_types.hpp")]
     elif tu == "open":
-        deps = [os.path.join(CSRC, n) for n in ("open.hpp", "march.hpp", "device.hpp")]
+        deps = [os.path.join(CSRC, n) for n in ("open.hpp", "march.hpp", "device.hpp", "plan_types.hpp")]
     elif tu == "resident":
-        deps = [os.path.join(CSRC, n) for n in ("resident.hpp", "device.hpp", "internal.hpp")]
+        deps = [os.path.join(CSRC, n) for n in ("resident.hpp", "device.hpp", "plan_types.hpp", "internal.hpp")]
     else:
         raise ValueError(f"unknown translation unit {tu!r}")
     return sorted({own, hdr, mk, *deps})

@@ -12,13 +12,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plan_types.hpp"  // Geo, HALO, CAVITY / CHANNEL / BACKSTEP
+
 namespace cfd {
 
-constexpr int CAVITY = 0, CHANNEL = 1, BACKSTEP = 2;
 #ifndef CFD_WAVE_MIN_WAVES
 #define CFD_WAVE_MIN_WAVES 3  // waves per SIMD the SOR wave kernel must fit (4 would cap VGPRs at 128 and spill)
 #endif
-constexpr int HALO = 8;           // halo rows stored per side (a fused pair of SOR iterations needs 7)
 constexpr int RES_SHARDS = 32;    // residual / max accumulators, one 128-B line each
 constexpr int SHARD_STRIDE = 16;  // doubles between shards (128 B)
 constexpr int RING = 16;          // residual ring slots (iteration k uses k & 15)
@@ -28,15 +28,6 @@ constexpr int RING = 16;          // residual ring slots (iteration k uses k & 1
 // window (at most two launches back, >= k-8) and this launch's own.
 constexpr int RING_AHEAD = 4;
 static_assert(4 + RING_AHEAD + 8 <= RING, "ring too small for the tested window and the cleared slots");
-
-struct Geo {
-  int nx, ny;      // global interior cells
-  int pitch;       // doubles per stored row
-  int row_lo;      // global row index of stored row 0
-  int nrows;       // stored rows
-  int j0, j1;      // owned interior rows (global, inclusive)
-  int wj0, wj1;    // owned rows incl. physical ghost rows on boundary strips
-};
 
 struct Coef {
   int case_id;

@@ -57,22 +57,7 @@ constexpr int LEXW_SHARDS = 8;
 #endif
 #define CFD_LEXW_MIN_WAVES(NS) ((NS) <= 2 ? CFD_LEXW_W2 : CFD_LEXW_W3)  // copies of the exceedance bitset (by block, ~XCD)
 
-// Output columns per wave. A value is exact after s half-sweeps on the wave's
-// columns [s, 127-s]; the residual evaluated in half-sweep h reads its east
-// neighbour's NEW value (column x+1 after h). At 4 sweeps (h up to 8) the last
-// output column must therefore be 127-9 = 118: output columns 8..117 (110,
-// lanes 4..58; 10-column right halo). Up to 3 sweeps: 8..119 (112, lanes
-// 4..59), the red-black kernels' PAIR_TWC. Rows likewise: a strip's stored
-// 8-row halo serves up to 3 sweeps (Solver::lexw_ns keeps strips at 3).
-// At 5 sweeps (the cavity on one strip) the left halo grows to 10 columns
-// (output column 10 reads column 9 after 9 half-sweeps) and the right one to
-// 12: output columns 10..115 (106, lanes 5..57). At 6 sweeps (h up to 12) the
-// halos are 12 and 14 columns: output columns 12..113 (102, lanes 6..56).
-__host__ __device__ constexpr int lexw_twc(int ns) {
-  return ns >= 6 ? 102 : ns == 5 ? 106 : ns == 4 ? 110 : PAIR_TWC;
-}
-__host__ __device__ constexpr int lexw_ch(int ns) { return ns >= 6 ? 12 : ns == 5 ? 10 : 8; }
-
+// (the output columns per wave, lexw_twc / lexw_ch: plan_types.hpp)
 // The source-row ring (LexRun::fr: rows R+1 .. R+2NS of f, read-only, each
 // lane reading back only what it wrote) lives in LDS for the deep cavity
 // launches: 40 VGPRs less per lane, which is what lets 5 sweeps fit 2 waves
@@ -96,48 +81,7 @@ __host__ __device__ constexpr bool lexw_lds(int kcase, int ns) {
 }
 __host__ __device__ constexpr int lexw_ring(int ns) { return ns <= 4 ? 8 : 16; }
 
-// Ramp-launch tiling: bands of `th` rows from row `row0`; band b holds the
-// column tiles ca..cb (the ones its rows touch), numbered from first: band[b]
-// = first << 16 | ca << 8 | cb. Waves map to tiles band by band, column tiles
-// side by side (their shared halo columns are read together from one L2),
-// with no empty tiles (a workgroup holds its slot until its last wave ends).
-constexpr int LEXW_RAMP_BANDS = 256;
-struct LexRamp {
-  int nb, th, row0;
-  int wsplit;  // 1: the wall column tiles (first, last) march each band as two half bands (two waves)
-  // the step: its crossing column tiles xa .. xa + xn - 1 march the bands that
-  // reach the block's edge (band rows blo .. blo + th - 1 with blo + th + xreach
-  // >= jb) as two half bands too (xn = 0: none)
-  int xa, xn, xreach;
-  unsigned band[LEXW_RAMP_BANDS];
-};
-
-// ramp launch: the column tile and half band (-1: the whole band) of wave o of
-// a band whose tiles are ca .. cb (split tiles take two consecutive waves)
-__host__ __device__ inline int lexw_ramp_waves(const LexRamp& rp, int ctiles, int b, int ca, int cb, int o,
-                                               int* ctile, int* half) {
-  int sp[4], n = 0;
-  if (rp.wsplit && ca == 0 && cb >= ca) sp[n++] = 0;
-  if (rp.xn > 0 && rp.row0 + (b + 1) * rp.th + rp.xreach >= 0)
-    for (int c = max(rp.xa, ca); c <= min(rp.xa + rp.xn - 1, cb); ++c)
-      if (c != 0 && c != ctiles - 1) sp[n++] = c;
-  if (rp.wsplit && cb == ctiles - 1 && cb > 0) sp[n++] = cb;
-  int extra = 0;
-  for (int q = 0; q < n; ++q) {
-    const int at = sp[q] - ca + extra;
-    if (o < at) break;
-    if (o == at || o == at + 1) {
-      *ctile = sp[q];
-      *half = o - at;
-      return n;
-    }
-    ++extra;
-  }
-  *ctile = ca + o - extra;
-  *half = -1;
-  return n;  // (the split tiles: the band has cb - ca + 1 + n waves)
-}
-
+// (the ramp-launch tiling, LexRamp / lexw_ramp_waves: plan_types.hpp)
 struct LexCtl {
   unsigned long long* bits;  // LEXW_SHARDS x words; bit q of the bitset <-> iteration q - kmax
   int words;                 // per shard
@@ -281,12 +225,6 @@ constexpr int LX_ACT = 1;
 // the ghost rows unchecked (lx_march)
 #ifndef CFD_LEXW_GROUPS
 #define CFD_LEXW_GROUPS 1
-#endif
-// A/B build only: every interior band of the open cases on the row-checked
-// march (one interior code path in the kernel: is the checked path slow for
-// its work or for the instruction cache it shares with the safe path?)
-#ifndef CFD_LEXW_ALLRC
-#define CFD_LEXW_ALLRC 0
 #endif
 constexpr int LX_SAMPLE = 2;  // sampled residual rows (lx_res_row)
 struct LxAct {
@@ -911,28 +849,7 @@ __device__ __forceinline__ void lx_march(const WaveCtx<CAVITY>& x, const LexCtx&
   if (lane == 0) lexw_flush(L, shard, Bd0 - 63 + L.kmax, b, 128);
 }
 
-// Owned rows of column tile `ct` whose output cells launch H0 touches: a cell
-// (j,i) is updated in one of the launch's half-sweeps or has its black
-// residual of half-sweep H0-1 evaluated (i+j <= H0+2NS-1 and i+j+2(K-1) >=
-// H0-1), or finished in the previous launch and must be copied into this
-// launch's output buffer (i+j+2(K-1) >= H0-2NS). Other rows hold their final
-// values in both buffers already.
-// Open cases: the ghost rows / columns too, the left / bottom ghosts active two
-// half-sweeps later than their position (lxo_row).
-__host__ __device__ inline void lexw_rows(const Geo& g, int H0, int K, int ns, int ct, int* lo, int* hi,
-                                          bool open = false) {
-  const int twc = lexw_twc(ns);
-  if (!open) {
-    const int cmin = max(ct * twc, 1), cmax = min(ct * twc + twc - 1, g.nx);
-    *lo = max(g.j0, H0 - 2 * ns - 2 * (K - 1) - cmax);
-    *hi = min(g.j1, H0 + 2 * ns - 1 - cmin);
-  } else {
-    const int cmin = max(ct * twc, 0), cmax = min(ct * twc + twc - 1, g.nx + 1);
-    *lo = max(g.wj0, H0 - 2 * ns - 2 * (K - 1) - cmax - 2);
-    *hi = min(g.wj1, H0 + 2 * ns - 1 - cmin);
-  }
-}
-
+// (the owned rows of a column tile that a launch touches, lexw_rows: plan_types.hpp)
 // diagnostic build only (CFD_LEXW_STAMPS=1, never the product library): per
 // launch (H0 / 2NS) and march path (0 wall tiles, 1 unmasked, 2 masked, 3
 // steady interior, 4 the step's block-crossing tiles on the masked march or
@@ -997,7 +914,7 @@ __global__ __launch_bounds__(256, RAMP ? 2 : CFD_LEXW_MIN_WAVES(NS)) void poisso
     const int ca = (e >> 8) & 255, cb = e & 255;
     // wall tiles (masked march, slower per step; they set the ramp launches'
     // time) and the step's crossing tiles at the block's edge: two waves each,
-    // one per half band (host: launch_lexw build)
+    // one per half band (host: plan.hpp lexw_launch_plan, build)
     int half;
     lexw_ramp_waves(rp, pl.ctiles, lo, ca, cb, tile - (int)(e >> 16), &ctile, &half);
     if (ctile > cb) return;

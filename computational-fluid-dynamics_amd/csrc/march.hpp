@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256, CFD_WAVE_MIN_WAVES) void poisson_wave_kernel(G
 // replays it with one single-iteration launch from this launch's input.
 
 constexpr int PAIR_H = 7;                     // row / column dependency depth of a pair
-constexpr int PAIR_TWC = 128 - 2 * 8;         // output columns per wave (8-column halos)
+// (PAIR_TWC, the output columns per wave: plan_types.hpp)
 
 #define CFD_SLOT(X) ((((ROT) + 4 - (X)) % 5 + 10) % 5)
 
@@ -908,53 +908,11 @@ __device__ __forceinline__ void wave_march_pair_edge(const WaveCtx<CASE>& x, int
 #define CFD_CAV_MIN_WAVES 3  // the cavity pair kernel fits 3 waves/SIMD with room (129 VGPRs)
 #endif
 
-// Tiling of one pair launch. Rows are covered in up to two ranges [lo0, hi0)
-// and [lo1, hi1) (the second may be empty): one launch for a whole strip, or,
-// on ranks that overlap the halo exchange, one launch for the interior rows
-// and one for the rows next to both neighbours. Every column tile splits each
-// range into bands; the first and last column tile (boundary columns, masked
-// march) use shorter bands of `the` rows.
-struct PairPlan {
-  int ctiles;
-  int th, nb0, nb1;    // interior column tiles: band height, bands in range 0 / 1
-  int the, nbe0, nbe1; // boundary column tiles
-  int lo0, hi0, lo1, hi1;
-  int cxa, cxb;        // step: column tiles across the step's column (+1; 0: none), banded like the boundary ones
-  // step, proof launches (open.hip) only: the block's column tiles. Tiles
-  // 1..nl lie left of the step's column, tiles nl+1..nl+ncx cross it (then
-  // cxa = cxb = 0: not boundary-class). Below the block, for both: nlf bands
-  // of th rows over [lo0, lz) march the interior-column path (away from the
-  // block edge), nle bands of `the` rows over [lz, le) the masked one, le =
-  // inlet_jmax + 2 (the block's lower edge row included). Above: the left
-  // tiles' nlt bands of `the` rows over [lt, hi0) when the range holds ghost
-  // row ny + 1 (refreshed from the block's top row; the block's interior rows
-  // between never change, both buffers hold them), the crossing tiles' nxt
-  // bands over [le, hi0) (fluid right of the block). ncx = 0: no such class.
-  int nl, ncx, nlf, nle, nlt, nxt, lz, le, lt;
-  // step, reference-order steady launches (lexw.hpp): the crossing column
-  // tiles xa .. xa + xn - 1 march their bands xb .. xb + xbn - 1 (those that
-  // reach the block's edge: the per-cell solid rules, ~1.7x the cycles per
-  // row) as xparts shorter bands, the extra parts' waves after the interior ones
-  int xa, xn, xb, xbn, xparts;
-};
-
-// column tiles banded as boundary tiles (masked march): the first and last,
-// and the step's mixed ones
-__host__ __device__ inline int plan_edge_tiles(const PairPlan& pl) {
-  return (pl.ctiles >= 2 ? 2 : 1) + (pl.cxa > 0) + (pl.cxb > 0);
-}
-
-// waves of a plan (every class)
-__host__ __device__ inline int plan_waves(const PairPlan& pl) {
-  const int ne = plan_edge_tiles(pl);
-  return ne * (pl.nbe0 + pl.nbe1) + pl.nl * (pl.nlf + pl.nle + pl.nlt) + pl.ncx * (pl.nlf + pl.nle + pl.nxt) +
-         (pl.ctiles - ne - pl.nl - pl.ncx) * (pl.nb0 + pl.nb1);
-}
-
+// (the tiling of one pair launch: PairPlan, plan_edge_tiles, plan_waves - plan_types.hpp)
 // PROOF (cavity): the convergence test of each sweep is the proof above
 // instead of the max-norm residual; the fields are the same bits.
 #ifndef CFD_PROOF_MIN_WAVES
-#define CFD_PROOF_MIN_WAVES 2  // proof-mode launches are planned for 2 waves per SIMD (Solver::init)
+#define CFD_PROOF_MIN_WAVES 2  // proof-mode launches are planned for 2 waves per SIMD (Solver::init: the budget plan.hpp's multi_plan gets)
 #endif
 // diagnostic build only (CFD_MARCH_STAMPS=1, never the product library): each
 // wave's march cycles with its tile, band and path (solver.hip cfd_march_stamps)

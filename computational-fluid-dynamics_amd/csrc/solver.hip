@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <variant>
 #include <vector>
 
@@ -26,14 +27,7 @@
 #include "smlex.hpp"
 #include "seqsum.hpp"
 #include "mg.hpp"
-
-// 1: the reference order's ramp launches march the wall column tiles as two
-// half bands each (lexw.hpp LexRamp::wsplit): the wall tiles' masked march set
-// the ramp launches' time (per-launch stamps); cavity 4096^2 704-717 -> 717-729
-// GLUPS, channel and 1024^2 neutral to +0.5 % (profiles/r4_lexw_stamps)
-#ifndef CFD_LEXW_WALL_SPLIT
-#define CFD_LEXW_WALL_SPLIT 1
-#endif
+#include "plan.hpp"
 
 namespace cfd {
 
@@ -51,12 +45,20 @@ static void check_launch(const char* what) {
   if (e != hipSuccess) throw Error(CFD_E_DEVICE, std::string("launch ") + what + ": " + hipGetErrorString(e));
 }
 
+// A value chosen at run time as a template argument: f gets it as a tag (std::integral_constant), and
+// decltype(tag)::value names the kernel instance. with_case: the three cases a Solver runs.
+template <int V>
+using Tag = std::integral_constant<int, V>;
+template <class F>
+static void with_case(int case_id, F&& f) {
+  if (case_id == CFD_CAVITY) f(Tag<CAVITY>{});
+  else if (case_id == CFD_CHANNEL) f(Tag<CHANNEL>{});
+  else f(Tag<BACKSTEP>{});
+}
+
 enum { B_P0 = 0, B_P1, B_F, B_US, B_VS, B_U, B_V, B_UC, B_VC, B_PL, B_P2, B_T, B_T2, NB };  // B_T/B_T2: Rayleigh-Benard only;  // B_PL: lex-mode initial field;
 // B_P2: third pressure buffer of the lagged convergence test (ranks)
 static int pbuf(int idx) { return idx == 0 ? B_P0 : idx == 1 ? B_P1 : B_P2; }
-
-constexpr int MARCH_MIN_TH = 24;   // minimum rows per band of a wave-march launch
-constexpr int OVL_ROWS = 16;       // rows next to each neighbour updated by the overlapped boundary launch
 
 struct Strip {
   Geo g{};
@@ -238,54 +240,16 @@ class Solver {
   cfd_timing T{};
   int resident_waves = 2048;  // wave-march tiles in flight (CUs x 4 SIMDs x waves per SIMD)
   int resident_pair_waves = 2048;  // the same for the two-iteration kernel
-  int pair_edge_pct = 45;          // boundary-column band length, % of the interior march (open cases; cavity: 80)
   int march_flags = 3;         // bit 0 alternate directions, bit 1 XCD-aware order, bit 3 column-major tile order
-  int march_min_th = MARCH_MIN_TH;
   int tent_th = 64;            // rows per band of the predictor's march
   int n_cu = 256;              // compute units of the device
 
   // cfd_sor_plan_info: the plans of the most recent solve, noted where its launches are planned
   // (launch_poisson, multi_overlapped, launch_lexw). Bookkeeping only: nothing reads it back.
-  // What multi_plan / wave_bands know about a plan beyond the PairPlan itself:
-  struct PlanNote {
-    int waves = 0, sweeps = 0, extra = 0, max_th = 1 << 30, tiles = 0;
-    bool budget_bands = false, shortened = false;
-    int clamped = 0;
-  };
-  cfd_sor_plan rep{};
-  // the entry of a plan in rep.plan (appended at its first launch; nullptr: the table is full)
-  cfd_sor_band_plan* rep_plan(int kind, const PairPlan& pl, const PlanNote& nt, bool proof) {
-    cfd_sor_band_plan b{};
-    b.kind = kind;
-    b.sweeps = nt.sweeps;
-    b.proof = proof ? 1 : 0;
-    b.waves = nt.waves;
-    b.lo0 = pl.lo0; b.hi0 = pl.hi0; b.lo1 = pl.lo1; b.hi1 = pl.hi1;
-    b.ctiles = pl.ctiles;
-    b.th = pl.th; b.nb0 = pl.nb0; b.nb1 = pl.nb1;
-    b.the = pl.the; b.nbe0 = pl.nbe0; b.nbe1 = pl.nbe1;
-    b.nl = pl.nl; b.ncx = pl.ncx;
-    b.tiles = nt.tiles;
-    b.extra = nt.extra;
-    b.max_th = nt.max_th;
-    b.budget_bands = nt.budget_bands;
-    b.shortened = nt.shortened;
-    b.clamped = nt.clamped;
-    b.march_order = kind == CFD_PLAN_LEXW ? 0 : (march_flags >> 3) & 1;
-    for (int q = 0; q < rep.n_plans; ++q) {
-      const cfd_sor_band_plan& a = rep.plan[q];
-      if (a.kind == b.kind && a.sweeps == b.sweeps && a.proof == b.proof && a.waves == b.waves && a.lo0 == b.lo0 &&
-          a.hi0 == b.hi0 && a.lo1 == b.lo1 && a.hi1 == b.hi1 && a.th == b.th && a.the == b.the && a.nb0 == b.nb0 &&
-          a.nbe0 == b.nbe0 && a.tiles == b.tiles && a.march_order == b.march_order)
-        return &rep.plan[q];
-    }
-    if (rep.n_plans == CFD_SOR_PLAN_MAX) {
-      ++rep.plans_dropped;
-      return nullptr;
-    }
-    rep.plan[rep.n_plans] = b;
-    return &rep.plan[rep.n_plans++];
-  }
+  PlanReport rep;
+  // The planner's input: the grid and the strips (init) and the planning knobs themselves, kept here and nowhere
+  // else (set_tuning_value). The planning - multi_plan, wave_bands, lexw_launch_plan ... - is plan.hpp's, over this.
+  PlanIn in;
 
   // cfd_set_tuning (include/cfd_amd.h enum cfd_tuning): launch planning only
   void set_tuning(int knob, int v) {
@@ -298,16 +262,16 @@ class Solver {
       case CFD_TUNE_PAIR_WPS: resident_pair_waves = std::max(1, std::min(v, 4)) * 4 * n_cu; break;
       case CFD_TUNE_WAVE_WPS: resident_waves = std::max(1, std::min(v, 4)) * 4 * n_cu; break;
       case CFD_TUNE_LEXW_WAVES: resident_lexw_waves = std::max(64, v); break;
-      case CFD_TUNE_LEXW_EDGE_PCT: lexw_edge_pct = std::max(10, std::min(100, v)); break;
-      case CFD_TUNE_PAIR_EDGE_PCT: pair_edge_pct = std::max(10, std::min(100, v)); break;
-      case CFD_TUNE_MARCH_MIN_TH: march_min_th = std::max(1, v); break;
+      case CFD_TUNE_LEXW_EDGE_PCT: in.lexw_edge_pct = std::max(10, std::min(100, v)); break;
+      case CFD_TUNE_PAIR_EDGE_PCT: in.pair_edge_pct = std::max(10, std::min(100, v)); break;
+      case CFD_TUNE_MARCH_MIN_TH: in.march_min_th = std::max(1, v); break;
       case CFD_TUNE_TENT_TH: tent_th = std::max(4, v); break;
-      case CFD_TUNE_LEXW_RAMP_PCT: lexw_ramp_pct = std::max(0, std::min(100, v)); break;
+      case CFD_TUNE_LEXW_RAMP_PCT: in.lexw_ramp_pct = std::max(0, std::min(100, v)); break;
       case CFD_TUNE_TILE_ROUNDS: tile_rounds = std::max(0, std::min(v, 16)); break;
-      case CFD_TUNE_MARCH_ORDER: march_flags = (march_flags & ~8) | (v ? 8 : 0); break;
-      case CFD_TUNE_LEXW_LEFT: lexw_left = v != 0; break;
+      case CFD_TUNE_MARCH_ORDER: march_flags = (march_flags & ~8) | (v ? 8 : 0), in.march_order = v ? 1 : 0; break;
+      case CFD_TUNE_LEXW_LEFT: in.lexw_left = v != 0; break;
       case CFD_TUNE_RESIDENT: res_knob = v != 0; break;
-      case CFD_TUNE_LEXW_UPDOWN: lexw_updown = v != 0; break;
+      case CFD_TUNE_LEXW_UPDOWN: in.lexw_updown = v != 0; break;
       default: throw Error(CFD_E_ARG, "unknown tuning knob");
     }
   }
@@ -320,10 +284,6 @@ class Solver {
   double* resmax = nullptr;
   hipEvent_t ev_f0 = nullptr, ev_f1 = nullptr;
   int resident_lexw_waves = 2048;
-  int lexw_edge_pct = 100;  // wall-tile band length, % of the interior band (cfd_tuning_default: 75 up to 2048 rows)
-  int lexw_ramp_pct = 0;    // ramp launches: bands at least this % of the steady plan's (CFD_TUNE_LEXW_RAMP_PCT)
-  bool lexw_left = true;    // backwards step: the left column tiles' class (CFD_TUNE_LEXW_LEFT)
-  bool lexw_updown = true;  // cavity steady launches: odd interior bands march up (CFD_TUNE_LEXW_UPDOWN)
   // the multi-block reference-order march (lexw.hpp): cavity (1-4 sweeps per
   // launch), channel and backwards step (4; 3 on strips). The step's solid
   // rules need a block of at least 2 columns and 2 rows (si >= 2, jb <= ny-1);
@@ -411,9 +371,6 @@ class Solver {
     }
     comm_group_end(comm, st);
   }
-  // rows one lexw wave marches beyond its band: the pipeline (2NS+1 each side) + parity row
-  static int lexw_extra(int ns) { return 2 * (2 * ns + 1) + 1; }
-
   // Rayleigh-Benard: the cavity's projection (P.case_id is set to CFD_CAVITY,
   // u_ref 0 = lid at rest) plus the temperature stage on tcur/tnext.
   bool thermal = false;
@@ -454,12 +411,10 @@ class Solver {
       wps = std::max(1, std::min(wps, 4));
       resident_waves = wps * 4 * prop.multiProcessorCount;
       int pps = 0;
-      if (P.case_id == CFD_CAVITY)  // resident waves of the launch the solve runs most
-        HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pps, poisson_multi_kernel<CAVITY, 3>, 256, 0));
-      else if (P.case_id == CFD_CHANNEL)
-        HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pps, poisson_multi_kernel<CHANNEL, 2>, 256, 0));
-      else
-        HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pps, poisson_multi_kernel<BACKSTEP, 2>, 256, 0));
+      with_case(P.case_id, [&](auto c) {  // resident waves of the launch the solve runs most: the cavity's 3 sweeps, else 2
+        constexpr int CASE = decltype(c)::value;
+        HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pps, poisson_multi_kernel<CASE, CASE == CAVITY ? 3 : 2>, 256, 0));
+      });
       pps = std::max(1, std::min(pps, 4));
       // device-independent plan defaults (params.cpp cfd_tuning_default):
       // cavity boundary-column bands 80 % of the interior march (lane-constant
@@ -480,16 +435,10 @@ class Solver {
         // instance of this (case, sweeps per launch), the smaller of the two
         // (sampled residual rows from 3 sweeps on, the capped solve's launches;
         // the LDS ring is static shared memory, so the query counts it)
-        const int ns = lexw_ns();
         int lps = 0;
-        if (P.case_id == CFD_CHANNEL) lps = ns == 3 ? lexw_blocks<CHANNEL, 3, true>() : lexw_blocks<CHANNEL, 4, true>();
-        else if (P.case_id == CFD_BACKSTEP) lps = ns == 3 ? lexw_blocks<BACKSTEP, 3, true>() : lexw_blocks<BACKSTEP, 4, true>();
-        else if (ns == 6) lps = lexw_blocks<CAVITY, 6, true>();
-        else if (ns == 5) lps = lexw_blocks<CAVITY, 5, true>();
-        else if (ns == 4) lps = lexw_blocks<CAVITY, 4, true>();
-        else if (ns == 1) lps = lexw_blocks<CAVITY, 1, false>();
-        else if (ns == 2) lps = lexw_blocks<CAVITY, 2, false>();
-        else lps = lexw_blocks<CAVITY, 3, true>();
+        lexw_instance(lexw_ns(), true, [&](auto c, auto n, auto sm) {
+          lps = lexw_blocks<decltype(c)::value, decltype(n)::value, decltype(sm)::value>();
+        });
         resident_lexw_waves = std::max(1, std::min(lps, 4)) * 4 * prop.multiProcessorCount;
       }
       resident_pair_waves = pps * 4 * prop.multiProcessorCount;
@@ -520,6 +469,8 @@ class Solver {
       part += (size_t)s.grid2d.x * s.grid2d.y;
     }
     npart = part;
+    in.case_id = P.case_id, in.nx = P.nx, in.ny = P.ny, in.step_i = P.step_i, in.inlet_jmax = P.inlet_jmax;
+    in.n_strips = (int)S.size();
     const size_t ringn = (size_t)RING * RES_SHARDS * SHARD_STRIDE;
     HIPC(hipMalloc(&ring, ringn * sizeof(double)));
     HIPC(hipMalloc(&srcmax, RES_SHARDS * SHARD_STRIDE * sizeof(double)));
@@ -626,33 +577,16 @@ class Solver {
       for (auto* p : s.b)
         if (p) (void)hipFree(p);
     S.clear();
-    for (double* p : {ring, srcmax, divmax, tolv, total, partials, resmax, cscr})
-      if (p) (void)hipFree(p);
-    ring = srcmax = divmax = tolv = total = partials = resmax = cscr = nullptr;
-    if (seqws) (void)hipFree(seqws);
-    if (seqcnt) (void)hipFree(seqcnt);
-    seqws = nullptr;
-    seqcnt = nullptr;
-    if (lexbits) (void)hipFree(lexbits);
-    lexbits = nullptr;
-    if (lexflags) (void)hipFree(lexflags);
-    lexflags = nullptr;
-    lexflags_n = 0;
-    if (smlex_ck) (void)hipFree(smlex_ck);
-    smlex_ck = nullptr;
-    for (auto*& x : res_x) {
-      if (x) (void)hipFree(x);
-      x = nullptr;
-    }
-    if (res_state) (void)hipFree(res_state);
-    res_state = nullptr;
-    res_state_n = 0;
-    if (res_bits) (void)hipFree(res_bits);
-    res_bits = nullptr;
-    res_bits_n = 0;
-    lexbits_words = 0;
-    if (stop) (void)hipFree(stop);
-    stop = nullptr;
+    for (double** p : {&ring, &srcmax, &divmax, &tolv, &total, &partials, &resmax, &cscr, &lexflags, &smlex_ck, &res_x[0],
+                       &res_x[1]})
+      free_null(*p);
+    free_null(seqws);
+    free_null(seqcnt);
+    free_null(lexbits);
+    free_null(res_state);
+    free_null(res_bits);
+    free_null(stop);
+    lexbits_words = lexflags_n = res_state_n = res_bits_n = 0;
     if (h_stat) (void)hipHostFree(h_stat);
     if (h_shard) (void)hipHostFree(h_shard);
     h_stat = nullptr;
@@ -728,6 +662,63 @@ class Solver {
   }
 
   bool multi() const { return S.size() > 1 || comm != nullptr; }
+
+  // ---- steps every engine shares ----
+  // a device buffer that only grows: at least `need` elements afterwards (what it held is not kept)
+  template <class E>
+  static void grow(E*& p, size_t& have, size_t need) {
+    if (have >= need) return;
+    if (p) HIPC(hipFree(p));
+    p = nullptr, have = 0;
+    HIPC(hipMalloc(&p, need * sizeof(E)));
+    have = need;
+  }
+  template <class E>
+  static void free_null(E*& p) noexcept {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
+  // the exceedance bits of a K-iteration solve: bit k + offset; waves touch iterations -(nx+ny)/2 .. K + (nx+ny)/2
+  void grow_lexbits(int K) {
+    grow(lexbits, lexbits_words, (size_t)LEXW_SHARDS * ((lexw_offset(in) + K + (P.nx + P.ny) / 2 + 256) / 64 + 2));
+  }
+  // tolv's first two values (tol_kernel). on_stream: copied on the stream and waited for; else a blocking copy
+  struct Tol { double tol, res0; };  // (the solve's tolerance, the initial residual)
+  Tol read_tol(bool on_stream) {
+    Tol t{};
+    if (on_stream) {
+      HIPC(hipMemcpyAsync(&t, tolv, sizeof t, hipMemcpyDeviceToHost, st));
+      HIPC(hipStreamSynchronize(st));
+    } else {
+      HIPC(hipMemcpy(&t, tolv, sizeof t, hipMemcpyDeviceToHost));
+    }
+    return t;
+  }
+  // the max over the shards of a device accumulator (RES_SHARDS x SHARD_STRIDE doubles); on_stream as above
+  double shard_max(const double* acc, bool on_stream) {
+    constexpr size_t bytes = RES_SHARDS * SHARD_STRIDE * sizeof(double);
+    if (on_stream) {
+      HIPC(hipMemcpyAsync(h_shard, acc, bytes, hipMemcpyDeviceToHost, st));
+      HIPC(hipStreamSynchronize(st));
+    } else {
+      HIPC(hipMemcpy(h_shard, acc, bytes, hipMemcpyDeviceToHost));
+    }
+    double m = 0.0;
+    for (int q = 0; q < RES_SHARDS; ++q) m = std::max(m, h_shard[q * SHARD_STRIDE]);
+    return m;
+  }
+  // the device time between ev_a and ev_b (both reached)
+  float elapsed_ms() {
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
+    return ms;
+  }
+  // interior cells this solver owns (every strip)
+  long long owned_cells() const {
+    long long n = 0;
+    for (auto& s : S) n += (long long)(s.g.j1 - s.g.j0 + 1) * P.nx;
+    return n;
+  }
 
   // ------------------------------------------------------------ halos --
   // Copy `depth` owned boundary rows of buffer b into the neighbours' halos.
@@ -854,119 +845,6 @@ class Solver {
     check_launch("tol");
   }
 
-  // Sizing of the wave-march kernels: column tiles of `twc` output columns,
-  // each split into bands so that one resident round covers the strip.
-  void wave_bands(int rows, int twc, int resident, int& ctiles, int& th, int& nbands) const {
-    ctiles = (P.nx + 2 + twc - 1) / twc;
-    const int per_tile = std::max(1, resident / (ctiles * (int)S.size()));
-    const int bands = std::max(1, std::min(per_tile, (rows + march_min_th - 1) / march_min_th));
-    th = (rows + bands - 1) / bands;
-    nbands = (rows + th - 1) / th;
-  }
-
-  // Rows one interior wave marches beyond its band (both sides together, plus
-  // the parity alignment row) for an n-sweep launch: the cavity's pipeline has
-  // depth 2n+1, the open cases' pair pipeline 7.
-  // an n-sweep launch that runs open.hip's proof march (its plans may carry the step's left class)
-  bool open_proof_n(int n) const { return P.case_id != CFD_CAVITY && n >= 3 && proof_launch; }
-
-  int march_extra(int n) const { return (P.case_id == CFD_CAVITY || n == 4) ? 2 * (2 * n + 1) + 1 : 15; }
-
-  // Tiling of an n-sweep launch over rows [lo0, hi0) + [lo1, hi1) with at most
-  // `waves` waves (one resident round). Interior column tiles: bands of th
-  // rows, marched in groups of 10 over th + march_extra rows, so th + extra is
-  // a multiple of 10. The two boundary column tiles march slower (masks):
-  // shorter bands, pair_edge_pct % of the interior march.
-  // left_class (the step's proof launches, open.hip): the column tiles over
-  // the step's block (left of its column and across it) become their own
-  // class (PairPlan::nl / ncx): interior-path bands below the block, short
-  // masked bands next to its lower edge and above it.
-  // note (optional): what cfd_sor_plan_info reports about the plan (written, never read here)
-  PairPlan multi_plan(int lo0, int hi0, int lo1, int hi1, int waves, int n, int max_th = 1 << 30,
-                      int edge_pct = -1, int twc = PAIR_TWC, int ex = -1, bool left_class = false,
-                      PlanNote* note = nullptr) const {
-    if (edge_pct < 0) edge_pct = pair_edge_pct;
-    PairPlan pl{};
-    pl.ctiles = (P.nx + 2 + twc - 1) / twc;
-    pl.lo0 = lo0; pl.hi0 = hi0; pl.lo1 = lo1; pl.hi1 = hi1;
-    if (P.case_id == CFD_BACKSTEP) {
-      // interior column tiles across the step's column (neither left of it,
-      // kernels.hpp: c0 + 128 <= step_i - 1, nor right, c0 > step_i + 1) march
-      // with per-cell masks: band them like the boundary tiles
-      int nx_found = 0;
-      for (int ct = 1; ct + 1 < pl.ctiles && nx_found < 2; ++ct) {
-        const int c0 = ct * PAIR_TWC - 8;
-        if (!(c0 > C.step_i + 1) && !(c0 + 128 <= C.step_i - 1)) {
-          (nx_found == 0 ? pl.cxa : pl.cxb) = ct + 1;
-          ++nx_found;
-        }
-      }
-    }
-    const int rows = (hi0 - lo0) + (hi1 - lo1);
-    const int rmax = std::max(hi0 - lo0, hi1 - lo1);
-    if (ex < 0) ex = march_extra(n);
-    auto nbands = [](int lo, int hi, int t) { return hi > lo ? (hi - lo + t - 1) / t : 0; };
-    // the block's column class (PairPlan::nl / ncx): column tiles 1 .. cxa-2
-    // (wholly left of the step's column) and the crossing ones; rows [lo0, lz)
-    // interior-column bands (every row the march reads below the block's
-    // lower edge row: open.hip cols_in), [lz, le) short masked bands, above
-    // that the top ghost row (left tiles) or every row (crossing tiles)
-    const int cx_last = pl.cxb > 0 ? pl.cxb - 1 : pl.cxa - 1;  // the last crossing tile
-    const bool lc = left_class && P.case_id == CFD_BACKSTEP && pl.cxa > 1 && cx_last < pl.ctiles - 1 && hi1 <= lo1;
-    if (lc) {
-      pl.nl = pl.cxa - 2;
-      pl.ncx = pl.cxb > 0 ? 2 : 1;
-      pl.cxa = pl.cxb = 0;  // (the crossing tiles leave the boundary class)
-      pl.lz = std::max(lo0, std::min(hi0, C.inlet_jmax - (2 * n + 2)));
-      pl.le = std::max(pl.lz, std::min(hi0, C.inlet_jmax + 2));
-      pl.lt = hi0;  // (ghost row ny + 1 in the range: set with `the` below)
-    }
-    auto left_bands = [&] {
-      if (!lc) return;
-      pl.nlf = nbands(lo0, pl.lz, pl.th);
-      pl.nle = nbands(pl.lz, pl.le, pl.the);
-      if (hi0 == P.ny + 2) pl.lt = std::max(pl.le, hi0 - pl.the);
-      pl.nlt = nbands(pl.lt, hi0, pl.the);
-      pl.nxt = nbands(pl.le, hi0, pl.the);
-    };
-    int nb = std::max(1, std::min(waves / std::max(1, pl.ctiles), (rows + march_min_th - 1) / march_min_th));
-    nb = std::max(nb, (rows + max_th - 1) / max_th);
-    const int nb_first = nb;
-    bool clamped = false;
-    for (;; --nb) {  // most interior bands whose tiles (boundary tiles included) fit one round
-      pl.th = std::max(1, std::min(rmax, ((rows + nb - 1) / nb + ex + 9) / 10 * 10 - ex));
-      if (pl.th > max_th) {  // (lexw: one wave marches at most max_th rows)
-        pl.th = max_th;
-        pl.the = std::max(8, std::min(rmax, (pl.th + ex) * edge_pct / 100 - ex));
-        pl.nb0 = nbands(lo0, hi0, pl.th);
-        pl.nb1 = nbands(lo1, hi1, pl.th);
-        pl.nbe0 = nbands(lo0, hi0, pl.the);
-        pl.nbe1 = nbands(lo1, hi1, pl.the);
-        left_bands();
-        clamped = true;
-        break;
-      }
-      pl.the = std::max(8, std::min(rmax, (pl.th + ex) * edge_pct / 100 - ex));
-      pl.nb0 = nbands(lo0, hi0, pl.th);
-      pl.nb1 = nbands(lo1, hi1, pl.th);
-      pl.nbe0 = nbands(lo0, hi0, pl.the);
-      pl.nbe1 = nbands(lo1, hi1, pl.the);
-      left_bands();
-      if (plan_waves(pl) <= waves || nb == 1) break;
-    }
-    if (note) {
-      note->waves = waves;
-      note->sweeps = n;
-      note->extra = ex;
-      note->max_th = max_th;
-      note->tiles = plan_waves(pl);
-      note->budget_bands = waves / std::max(1, pl.ctiles) < (rows + march_min_th - 1) / march_min_th;
-      note->shortened = nb < nb_first;
-      note->clamped = clamped ? 1 : (pl.th == rmax && ((pl.th + ex) % 10) != 0) ? 2 : 0;
-    }
-    return pl;
-  }
-
   // One launch of poisson_multi_kernel: iterations k .. k+n-1 (n = 2, or 3 for
   // the cavity), testing iterations [ka, kb] first (empty: ka > kb).
   template <int CASE>
@@ -1014,29 +892,16 @@ class Solver {
     }
     for (size_t q = 0; q < S.size(); ++q) {
       const Geo& g = S[q].g;
-      const int rows = g.wj1 - g.wj0 + 1;
-      int ctiles, th, nbands;
       PlanNote nt;
       if (n >= 2) {
-        const PairPlan pl = multi_plan(g.wj0, g.wj1 + 1, 0, 0, resident_pair_waves / (int)S.size(), n, 1 << 30, -1,
-                                       PAIR_TWC, -1, open_proof_n(n), &nt);
-        if (cfd_sor_band_plan* b = rep_plan(CFD_PLAN_PAIR, pl, nt, proof_launch && !replay)) ++b->launches;
+        const PairPlan pl = multi_plan(in, g.wj0, g.wj1 + 1, 0, 0, resident_pair_waves / (int)S.size(), n, 1 << 30, -1,
+                                       PAIR_TWC, -1, open_proof_n(in, n, proof_launch), &nt);
+        rep.launched(in, CFD_PLAN_PAIR, pl, nt, proof_launch && !replay);
         launch_multi<CASE>(n, pl, g, pin[q], pout[q], S[q].b[B_F], ctl, k, ka, kb, st, replay);
       } else {
-        wave_bands(rows, 128 - 8, resident_waves, ctiles, th, nbands);
-        {  // (the report's view of wave_bands: one class of ctiles x nbands tiles)
-          PairPlan pw{};
-          pw.ctiles = ctiles;
-          pw.th = pw.the = th;
-          pw.nb0 = pw.nbe0 = nbands;
-          pw.lo0 = g.wj0; pw.hi0 = g.wj1 + 1;
-          nt.waves = resident_waves / (int)S.size();
-          nt.sweeps = 1;
-          nt.extra = 0;
-          nt.tiles = ctiles * nbands;
-          nt.budget_bands = std::max(1, resident_waves / (ctiles * (int)S.size())) < (rows + march_min_th - 1) / march_min_th;
-          if (cfd_sor_band_plan* b = rep_plan(CFD_PLAN_WAVE, pw, nt, false)) ++b->launches;
-        }
+        int ctiles, th, nbands;
+        wave_bands(in, g.wj1 - g.wj0 + 1, 128 - 8, resident_waves, ctiles, th, nbands);
+        rep.launched(in, CFD_PLAN_WAVE, wave_report(in, g, resident_waves, ctiles, th, nbands, nt), nt, false);
         const int nblk = (ctiles * nbands + 3) / 4;
         poisson_wave_kernel<CASE><<<nblk, 256, 0, st>>>(g, C, pin[q], pout[q], S[q].b[B_F], ctl, k, ka, kb, th, ctiles,
                                                          nbands, march_flags | (replay ? 4 : 0) | (window_proof ? 128 : 0));
@@ -1101,19 +966,13 @@ class Solver {
       HIPC(hipStreamWaitEvent(st_b, ev_int[pe], 0));
       flush_allreduce(st_b);  // launch m-1's residuals, tested by launch m+1
     }
-    PairPlan pb{};
-    pb.ctiles = (P.nx + 2 + PAIR_TWC - 1) / PAIR_TWC;
-    pb.th = pb.the = OVL_ROWS;
-    pb.lo0 = g.wj0; pb.hi0 = g.wj0 + lo_b;
-    pb.lo1 = g.wj1 + 1 - hi_b; pb.hi1 = g.wj1 + 1;
-    pb.nb0 = pb.nbe0 = lo_b ? 1 : 0;
-    pb.nb1 = pb.nbe1 = hi_b ? 1 : 0;
+    const PairPlan pb = overlap_boundary_plan(in, g, lo_b, hi_b);
     launch_multi<CASE>(n, pb, g, pin, pout, s.b[B_F], ctl, k, ka, kb, st_b);
     if (m > 0) HIPC(hipStreamWaitEvent(st, ev_bnd[pe], 0));
     PlanNote nt;
-    const PairPlan pi = multi_plan(g.wj0 + lo_b, g.wj1 + 1 - hi_b, 0, 0, resident_pair_waves - 2 * pb.ctiles, n,
-                                   1 << 30, -1, PAIR_TWC, -1, open_proof_n(n), &nt);
-    if (cfd_sor_band_plan* b = rep_plan(CFD_PLAN_INTERIOR, pi, nt, proof_launch)) ++b->launches;
+    const PairPlan pi = multi_plan(in, g.wj0 + lo_b, g.wj1 + 1 - hi_b, 0, 0, resident_pair_waves - 2 * pb.ctiles, n,
+                                   1 << 30, -1, PAIR_TWC, -1, open_proof_n(in, n, proof_launch), &nt);
+    rep.launched(in, CFD_PLAN_INTERIOR, pi, nt, proof_launch);
     launch_multi<CASE>(n, pi, g, pin, pout, s.b[B_F], ctl, k, ka, kb, st);
     check_launch("poisson (overlapped)");
     HIPC(hipEventRecord(ev_int[e], st));
@@ -1132,9 +991,7 @@ class Solver {
     const int bin = pbuf((base + m) % nbufs());
     const int bout = pbuf((base + m + 1) % nbufs());
     if (overlap && n >= 2 && !replay) {
-      if (P.case_id == CFD_CAVITY) multi_overlapped<CAVITY>(m, k, n, ka, kb, bin, bout);
-      else if (P.case_id == CFD_CHANNEL) multi_overlapped<CHANNEL>(m, k, n, ka, kb, bin, bout);
-      else multi_overlapped<BACKSTEP>(m, k, n, ka, kb, bin, bout);
+      with_case(P.case_id, [&](auto c) { multi_overlapped<decltype(c)::value>(m, k, n, ka, kb, bin, bout); });
       return;
     }
     join_b();
@@ -1146,10 +1003,28 @@ class Solver {
       pin[q] = S[q].b[bin];
       pout[q] = S[q].b[bout];
     }
-    if (P.case_id == CFD_CAVITY) launch_poisson<CAVITY>(pin.data(), pout.data(), k, n, ka, kb, replay);
-    else if (P.case_id == CFD_CHANNEL) launch_poisson<CHANNEL>(pin.data(), pout.data(), k, n, ka, kb, replay);
-    else launch_poisson<BACKSTEP>(pin.data(), pout.data(), k, n, ka, kb, replay);
+    with_case(P.case_id, [&](auto c) { launch_poisson<decltype(c)::value>(pin.data(), pout.data(), k, n, ka, kb, replay); });
     if (comm && comm->nranks > 1 && !replay) allreduce_slots(k, n, st);
+  }
+
+  // The finish of the one-workgroup solves (solve_lex, solve_small, solve_smlex), whose kernel leaves its iterations
+  // in stop[0] and its residual in total[2]: timing, cfd_step_info; returns the iterations (count_sweeps: as sweeps too)
+  int finish_one_workgroup(cfd_step_info* out, bool count_sweeps) {
+    HIPC(hipEventRecord(ev_b, st));
+    int iters = 0;
+    double res = 0;
+    HIPC(hipMemcpyAsync(&iters, stop, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&res, total + 2, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    T.poisson_ms += elapsed_ms();
+    T.poisson_launches += 1;
+    if (count_sweeps) T.poisson_sweeps += iters;
+    T.poisson_cell_updates += (long long)P.nx * P.ny * iters;
+    if (out) {
+      out->sor_iterations = iters;
+      out->residual = res;
+    }
+    return iters;
   }
 
   // solverPressurePoisson (cavity-01.cpp:609-690, channel-01.cpp:635-688,
@@ -1168,67 +1043,18 @@ class Solver {
     }
     solve_tolerance();
     HIPC(hipMemcpyAsync(s.b[B_PL], X0, bytes, hipMemcpyDeviceToDevice, st));
-    int* d_it = stop;
-    double* d_res = total + 2;
     HIPC(hipEventRecord(ev_a, st));
-    if (P.case_id == CFD_CAVITY)
-      poisson_lex_kernel<CAVITY><<<1, 1024, 0, st>>>(s.g, C, X0, X1, s.b[B_PL], s.b[B_F], tolv, P.max_iters, d_it, d_res);
-    else if (P.case_id == CFD_CHANNEL)
-      poisson_lex_kernel<CHANNEL><<<1, 1024, 0, st>>>(s.g, C, X0, X1, s.b[B_PL], s.b[B_F], tolv, P.max_iters, d_it, d_res);
-    else
-      poisson_lex_kernel<BACKSTEP><<<1, 1024, 0, st>>>(s.g, C, X0, X1, s.b[B_PL], s.b[B_F], tolv, P.max_iters, d_it, d_res);
+    with_case(P.case_id, [&](auto c) {
+      poisson_lex_kernel<decltype(c)::value><<<1, 1024, 0, st>>>(s.g, C, X0, X1, s.b[B_PL], s.b[B_F], tolv, P.max_iters, stop,
+                                                                 total + 2);
+    });
     check_launch("poisson_lex");
-    HIPC(hipEventRecord(ev_b, st));
-    int iters = 0;
-    double res = 0;
-    HIPC(hipMemcpyAsync(&iters, d_it, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(&res, d_res, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    T.poisson_ms += ms;
-    T.poisson_launches += 1;
-    T.poisson_cell_updates += (long long)P.nx * P.ny * iters;
-    pcur = (base + iters) & 1;
-    if (out) {
-      out->sor_iterations = iters;
-      out->residual = res;
-    }
+    pcur = (base + finish_one_workgroup(out, false)) & 1;  // (this engine alone adds nothing to poisson_sweeps)
   }
 
   // ---- lexicographic order, multi-block (lexw.hpp) ----
-  int lexw_offset() const { return (P.nx + P.ny) / 2 + 192; }
-  static int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-  // iterations whose residual every cell has contributed after launch m (H0 = 2 + 2NS m)
-  int lexw_done(int m, int ns) const { return m < 0 ? 0 : floordiv(2 + 2 * ns * m + 2 * ns - 2 - P.nx - P.ny, 2) + 1; }
-
-  // steady: every cell active in every half-sweep of the launch and in the
-  // previous launch's last one (no activity masks: the leaner kernel)
-  // backwards step, reference order: the block's ghost constants set before
-  // the march (lexw.hpp step_presolid_kernel), so that the column tiles left
-  // of the step's column end at the block's bottom row and march as a channel
-  // below it (flags bit 3; CFD_TUNE_LEXW_LEFT 0: the per-cell masked march)
-#ifndef CFD_LEXW_XSPLIT
-#define CFD_LEXW_XSPLIT 3
-#endif
-  // the step's interior column tiles that cross its column (the per-cell solid
-  // rules at the block's edge): xa .. xa + xn - 1, xa = -1 if none
-  void lexw_cross_tiles(int ns, const PairPlan& pl, int* xa, int* xn) const {
-    const int twc = lexw_twc(ns), ch = lexw_ch(ns), si = C.step_i;
-    *xa = -1;
-    *xn = 0;
-    for (int ct = 1; ct + 1 < pl.ctiles; ++ct) {
-      const int c0 = ct * twc - ch;
-      const bool left = c0 + 127 <= si - 1 && lexw_left_class();
-      if (!left && c0 <= si + 1) {
-        if (*xa < 0) *xa = ct;
-        *xn = ct - *xa + 1;
-      }
-    }
-  }
-  bool lexw_left_class() const { return P.case_id == CFD_BACKSTEP && lexw_left; }
   void lexw_presolid() {
-    if (!lexw_left_class()) return;
+    if (!lexw_left_class(in)) return;
     for (auto& s : S)
       for (int b : {0, 1}) {
         const int n = std::max(C.step_i, P.ny) + 1;
@@ -1237,232 +1063,48 @@ class Solver {
       }
   }
 
-  // cfd_sor_plan_info, host only: which marches poisson_lexw_kernel's decode gives the tiles of a
-  // launch - the kernel's own tests restated (lexw.hpp), so that the report says what ran.
-  // An interior band [y0, y1) of a plain open-case column tile is row-checked (never marched up):
-  bool lexw_row_checked(int ns, const Geo& g, int y0, int y1, bool left) const {
-    const int H = 2 * ns + 1;
-    const int rmin = std::max(g.row_lo, 0);
-    int rmax = std::min(g.row_lo + g.nrows - 1, g.ny + 1);
-    const int jg = left ? C.inlet_jmax + 1 : g.ny + 1;
-    if (left) rmax = std::min(rmax, C.inlet_jmax + 2);
-    return CFD_LEXW_ALLRC || !(y0 - H + 1 > rmin && y1 + H + 2 * ns < std::min(rmax, jg));
-  }
-  // a steady launch: the interior column tiles of the step's left class, and the odd interior bands
-  // that march up in the plain interior column tiles (neither left class nor crossing)
-  void lexw_steady_classes(int ns, const PairPlan& pl, const Geo& g, bool updown, int* left_tiles, int* up_bands) const {
-    const int twc = lexw_twc(ns), ch = lexw_ch(ns);
-    int nleft = 0, plain = 0;
-    for (int ct = 1; ct + 1 < pl.ctiles; ++ct) {
-      const int c0 = ct * twc - ch;
-      if (P.case_id != CFD_BACKSTEP) ++plain;
-      else if (c0 + 127 <= C.step_i - 1 && lexw_left_class()) ++nleft;
-      else if (c0 > C.step_i + 1) ++plain;
-    }
-    int up = 0;
-    if (updown && plain > 0)
-      for (int b = 1; b < pl.nb0 + pl.nb1; b += 2) {
-        const bool r0 = b < pl.nb0;
-        const int y0 = r0 ? pl.lo0 + b * pl.th : pl.lo1 + (b - pl.nb0) * pl.th;
-        const int y1 = std::min(y0 + pl.th, r0 ? pl.hi0 : pl.hi1);
-        if (y0 < y1 && (P.case_id == CFD_CAVITY || !lexw_row_checked(ns, g, y0, y1, false))) ++up;
+  // The instances of poisson_lexw_kernel: the channel and the step at 3 (strips) and 4 sweeps per launch, the cavity
+  // at 1 - 6; sampled residual rows (SAMPLE) from 3 sweeps on - 1 and 2 sweeps evaluate every row. f gets (case,
+  // sweeps, sample) as tags; the occupancy query (init) and the launch (launch_lexw) both come through here.
+  template <class F>
+  void lexw_instance(int ns, bool sample, F&& f) const {
+    auto sampled = [&](auto c, auto n) {
+      if constexpr (decltype(n)::value >= 3)
+        if (sample) return f(c, n, std::true_type{});
+      return f(c, n, std::false_type{});
+    };
+    with_case(P.case_id, [&](auto c) {
+      if constexpr (decltype(c)::value != CAVITY) {
+        if (ns == 3) sampled(c, Tag<3>{});  // (strips)
+        else sampled(c, Tag<4>{});
+      } else {
+        if (ns == 6) sampled(c, Tag<6>{});
+        else if (ns == 5) sampled(c, Tag<5>{});
+        else if (ns == 4) sampled(c, Tag<4>{});
+        else if (ns == 1) sampled(c, Tag<1>{});
+        else if (ns == 2) sampled(c, Tag<2>{});
+        else sampled(c, Tag<3>{});
       }
-    *left_tiles = nleft;
-    *up_bands = up;
-  }
-  // a ramp launch: does some tile take the upward march (an odd band's whole-band interior tile,
-  // wholly active in every half-sweep the launch evaluates, unmasked and unchecked)?
-  bool lexw_ramp_up(int ns, const PairPlan& pl, const Geo& g, const LexRamp& rp,
-                    const std::vector<std::pair<int, int>>& rr, int H0, int K) const {
-    const bool open = P.case_id != CFD_CAVITY;
-    const int H = 2 * ns + 1, twc = lexw_twc(ns), ch = lexw_ch(ns), glo = open ? 0 : 1;
-    const int Hend = H0 + 2 * ns - 1, last = 2 * (K - 1) + (open ? 2 : 0);
-    for (int b = 1; b < rp.nb; b += 2) {
-      const unsigned e = rp.band[b];
-      const int ca = (e >> 8) & 255, cb = e & 255;
-      const bool xsplit = rp.xn > 0 && rp.row0 + (b + 1) * rp.th + rp.xreach >= 0;  // (lexw_ramp_waves: half bands)
-      for (int c = std::max(ca, 1); c <= std::min(cb, pl.ctiles - 2); ++c) {
-        if (xsplit && c >= rp.xa && c < rp.xa + rp.xn) continue;
-        const int y0 = std::max(rp.row0 + b * rp.th, rr[c].first);
-        int y1 = std::min(rp.row0 + (b + 1) * rp.th, rr[c].second + 1);
-        const int c0 = c * twc - ch;
-        bool left = false;
-        if (P.case_id == CFD_BACKSTEP && c0 + 127 <= C.step_i - 1 && lexw_left_class()) {
-          left = c0 >= 1;
-          y1 = std::min(y1, C.inlet_jmax + 2);
-        }
-        if (y0 >= y1) continue;
-        const int rlo = std::max(std::max(y0 - H - 1, glo), g.row_lo);
-        const int rhi = std::min(std::min(y1 + H, g.ny + 1 - glo), g.row_lo + g.nrows - 1);
-        const int clo = std::max(c0, glo), chi = std::min(c0 + 127, g.nx + 1 - glo);
-        const int smin = clo + rlo, smax = chi + rhi;
-        if (smin > Hend || smax + last < H0 - 2 * ns) continue;
-        if (!(open ? (c0 >= 1 && c0 + 127 <= g.nx) : (clo == c0 && chi == c0 + 127))) continue;  // (cols_in)
-        if (!open) {
-          if (smax <= H0 - 2 && Hend <= smin + last) return true;
-          continue;
-        }
-        if (P.case_id == CFD_BACKSTEP && !left) {
-          const int jb = C.inlet_jmax + 1, si = C.step_i;
-          if (c0 + 127 <= si - 1 && y0 - H - 1 >= jb + 1 && y1 + H + 2 * ns + 1 <= g.ny) continue;  // (solids only)
-          if (y1 + H + 2 * ns + 1 >= jb - 1 && c0 <= si + 1) continue;                               // (the general tiles)
-        }
-        if (!lexw_row_checked(ns, g, y0, y1, left) && smax <= H0 - 2 && Hend <= smin + 2 * (K - 1)) return true;
-      }
-    }
-    return false;
+    });
   }
 
   void launch_lexw(int ns, bool steady, bool sample, const PairPlan& pl, const Geo& g, const double* pin,
                    double* pout, const double* f, const LexCtl& L, int H0, int K, int ka, int kb, bool replay,
                    int waves, const PlanNote& nt) {
-    const int fl = (replay ? 4 : 0) | (lexw_left_class() ? 8 : 0) | (lexw_updown ? 16 : 0);
-    cfd_sor_band_plan* const rb = rep_plan(CFD_PLAN_LEXW, pl, nt, false);  // (cfd_sor_plan_info)
-    const int ne = pl.ctiles >= 2 ? 2 : 1;
-    int ntiles = ne * (pl.nbe0 + pl.nbe1) + (pl.ctiles - ne) * (pl.nb0 + pl.nb1);
-    LexRamp rp{};
-    if (!steady) {
-      // ramp launch: tile only the rows it touches (lexw_rows), bands of the
-      // shortest height whose tiles fit one resident round, at most the
-      // steady plan's (at that every ramp launch fits: it touches fewer rows)
-      int rl = 1 << 30, rh = -1;
-      long long tot = 0;
-      std::vector<std::pair<int, int>> rr(pl.ctiles);
-      for (int c = 0; c < pl.ctiles; ++c) {
-        lexw_rows(g, H0, K, ns, c, &rr[c].first, &rr[c].second, P.case_id != CFD_CAVITY);
-        if (rr[c].second >= rr[c].first) {
-          rl = std::min(rl, rr[c].first);
-          rh = std::max(rh, rr[c].second);
-          tot += rr[c].second - rr[c].first + 1;
-        }
-      }
-      if (rh < rl) return;
-      const int ex = lexw_extra(ns);
-      rp.wsplit = CFD_LEXW_WALL_SPLIT;
-      if (P.case_id == CFD_BACKSTEP && CFD_LEXW_XSPLIT > 1) {  // the step's crossing tiles (as the steady split)
-        int xa, xn;
-        lexw_cross_tiles(ns, pl, &xa, &xn);
-        if (xa >= 0) {
-          rp.xa = xa;
-          rp.xn = xn;
-          rp.xreach = 4 * ns + 4 - (C.inlet_jmax + 1);
-        }
-      }
-      auto build = [&](int th) {  // fills rp for band height th; returns the tile count
-        rp.th = th;
-        rp.row0 = rl;
-        rp.nb = (rh - rl) / th + 1;
-        int n = 0;
-        for (int b = 0; b < rp.nb; ++b) {
-          const int blo = rl + b * th, bhi = blo + th - 1;
-          int ca = -1, cb = -2;
-          for (int c = 0; c < pl.ctiles; ++c)
-            if (std::max(blo, rr[c].first) <= std::min(bhi, rr[c].second)) {
-              if (ca < 0) ca = c;
-              cb = c;
-            }
-          if (ca < 0) ca = 0, cb = -1;  // (an empty band: no tiles)
-          rp.band[b] = ((unsigned)n << 16) | ((unsigned)ca << 8) | (unsigned)(cb < 0 ? 0 : cb);
-          if (cb < 0) rp.band[b] = ((unsigned)n << 16) | 1u << 8;  // ca 1 > cb 0: empty
-          n += std::max(0, cb - ca + 1);
-          if (cb >= ca) {  // a second wave per split tile (lexw.hpp lexw_ramp_waves: half bands)
-            int ct, hf;
-            n += lexw_ramp_waves(rp, pl.ctiles, b, ca, cb, 0, &ct, &hf);
-          }
-        }
-        return n;
+    const int fl = (replay ? 4 : 0) | (lexw_left_class(in) ? 8 : 0) | (in.lexw_updown ? 16 : 0);
+    const LexLaunch ll = lexw_launch_plan(in, ns, steady, pl, g, H0, K, waves);
+    if (ll.too_wide) throw Error(CFD_E_ARG, "lexicographic ordering: grid too wide");
+    rep.lexw_launched(in, ns, steady, sample, pl, nt, g, ll, H0, K);  // (cfd_sor_plan_info)
+    if (ll.ntiles == 0) return;
+    const dim3 grid((ll.ntiles + 3) / 4);
+    lexw_instance(ns, sample, [&](auto c, auto n, auto sm) {
+      auto go = [&](auto ramp) {
+        poisson_lexw_kernel<decltype(c)::value, decltype(n)::value, decltype(ramp)::value, decltype(sm)::value>
+            <<<grid, 256, 0, st>>>(g, C, pin, pout, f, L, H0, K, ka, kb, ll.plx, fl, ll.rp);
       };
-      int th = (int)std::max<long long>(1, (tot + waves - 1) / std::max(1, waves));
-      // (a floor on the band height trades idle wave slots for less pipeline fill per output row)
-      const bool by_floor = pl.th * lexw_ramp_pct / 100 > th;  // (by_floor .. fell_back: cfd_sor_plan_info)
-      th = std::max(th, pl.th * lexw_ramp_pct / 100);
-      th = std::max(1, (th + ex + 9) / 10 * 10 - ex);
-      bool grown_bands = false, grown_tiles = false, fell_back = false;
-      while ((rh - rl) / th + 1 > LEXW_RAMP_BANDS) {
-        th += 10;
-        grown_bands = true;
-      }
-      ntiles = build(th);
-      while (th < pl.th && ntiles > waves) {
-        ntiles = build(th += 10);
-        grown_tiles = true;
-      }
-      if (th > pl.th) {
-        ntiles = build(th = std::max(pl.th, (rh - rl) / LEXW_RAMP_BANDS + 1));
-        fell_back = true;
-      }
-      if (pl.ctiles > 255 || ntiles >= 65536) throw Error(CFD_E_ARG, "lexicographic ordering: grid too wide");
-      if (ntiles > 0) {
-        ++rep.ramp_launches;
-        rep.ramp_th_min = rep.ramp_th_min ? std::min(rep.ramp_th_min, rp.th) : rp.th;
-        rep.ramp_th_max = std::max(rep.ramp_th_max, rp.th);
-        rep.ramp_nb_max = std::max(rep.ramp_nb_max, rp.nb);
-        rep.ramp_tiles_max = std::max(rep.ramp_tiles_max, ntiles);
-        ++(by_floor ? rep.ramp_by_floor : rep.ramp_by_budget);
-        rep.ramp_grown_bands += grown_bands;
-        rep.ramp_grown_tiles += grown_tiles;
-        rep.ramp_fallback += fell_back;
-        if ((fl & 16) && sample && !rep.ramp_up) rep.ramp_up = lexw_ramp_up(ns, pl, g, rp, rr, H0, K) ? 1 : 0;
-      }
-    }
-    // the step's steady launches: the crossing column tiles' bands that reach
-    // the block's edge as CFD_LEXW_XSPLIT shorter bands (lexw.hpp; they set
-    // the launch's time: profiles/r5/step_8192x512_lex_stamps.json)
-    PairPlan plx = pl;
-    if (steady && P.case_id == CFD_BACKSTEP && CFD_LEXW_XSPLIT > 1 && pl.nb1 == 0 && pl.ctiles >= 3) {
-      const int jb = C.inlet_jmax + 1;
-      int xa, xn;
-      lexw_cross_tiles(ns, pl, &xa, &xn);
-      int xb = -1;
-      for (int b = 0; b < pl.nb0 && xb < 0; ++b)
-        if (std::min(pl.lo0 + (b + 1) * pl.th, pl.hi0) + 4 * ns + 4 >= jb) xb = b;
-      if (xa >= 0 && xb >= 0) {
-        plx.xa = xa;
-        plx.xn = xn;
-        plx.xb = xb;
-        plx.xbn = pl.nb0 - xb;
-        plx.xparts = CFD_LEXW_XSPLIT;
-        ntiles += plx.xn * plx.xbn * (plx.xparts - 1);
-      }
-    }
-    if (steady && rb && ntiles > 0) {  // (cfd_sor_plan_info: what this steady launch runs)
-      ++rb->launches;
-      rb->launch_tiles = ntiles;
-      rb->xn = plx.xn;
-      rb->xbn = plx.xbn;
-      lexw_steady_classes(ns, pl, g, (fl & 16) && sample, &rb->left_tiles, &rb->up_bands);
-    }
-    if (ntiles == 0) return;
-    const dim3 grid((ntiles + 3) / 4);
-#define CFD_LEXW_LAUNCH(CASE, NS, R, SM) \
-  poisson_lexw_kernel<CASE, NS, R, SM><<<grid, 256, 0, st>>>(g, C, pin, pout, f, L, H0, K, ka, kb, plx, fl, rp)
-    // (sampled residual rows: the 3-sweep kernels, the default; 1 and 2 sweeps evaluate every row)
-    if (P.case_id == CFD_BACKSTEP && ns == 3) {  // (strips)
-      if (sample) { if (steady) CFD_LEXW_LAUNCH(BACKSTEP, 3, false, true); else CFD_LEXW_LAUNCH(BACKSTEP, 3, true, true); }
-      else { if (steady) CFD_LEXW_LAUNCH(BACKSTEP, 3, false, false); else CFD_LEXW_LAUNCH(BACKSTEP, 3, true, false); }
-    } else if (P.case_id == CFD_BACKSTEP) {
-      if (sample) { if (steady) CFD_LEXW_LAUNCH(BACKSTEP, 4, false, true); else CFD_LEXW_LAUNCH(BACKSTEP, 4, true, true); }
-      else { if (steady) CFD_LEXW_LAUNCH(BACKSTEP, 4, false, false); else CFD_LEXW_LAUNCH(BACKSTEP, 4, true, false); }
-    } else if (P.case_id == CFD_CHANNEL && ns == 3) {  // (strips)
-      if (sample) { if (steady) CFD_LEXW_LAUNCH(CHANNEL, 3, false, true); else CFD_LEXW_LAUNCH(CHANNEL, 3, true, true); }
-      else { if (steady) CFD_LEXW_LAUNCH(CHANNEL, 3, false, false); else CFD_LEXW_LAUNCH(CHANNEL, 3, true, false); }
-    } else if (P.case_id == CFD_CHANNEL) {
-      if (sample) { if (steady) CFD_LEXW_LAUNCH(CHANNEL, 4, false, true); else CFD_LEXW_LAUNCH(CHANNEL, 4, true, true); }
-      else { if (steady) CFD_LEXW_LAUNCH(CHANNEL, 4, false, false); else CFD_LEXW_LAUNCH(CHANNEL, 4, true, false); }
-    } else if (ns == 6) {
-      if (sample) { if (steady) CFD_LEXW_LAUNCH(CAVITY, 6, false, true); else CFD_LEXW_LAUNCH(CAVITY, 6, true, true); }
-      else { if (steady) CFD_LEXW_LAUNCH(CAVITY, 6, false, false); else CFD_LEXW_LAUNCH(CAVITY, 6, true, false); }
-    } else if (ns == 5) {
-      if (sample) { if (steady) CFD_LEXW_LAUNCH(CAVITY, 5, false, true); else CFD_LEXW_LAUNCH(CAVITY, 5, true, true); }
-      else { if (steady) CFD_LEXW_LAUNCH(CAVITY, 5, false, false); else CFD_LEXW_LAUNCH(CAVITY, 5, true, false); }
-    } else if (ns == 4) {
-      if (sample) { if (steady) CFD_LEXW_LAUNCH(CAVITY, 4, false, true); else CFD_LEXW_LAUNCH(CAVITY, 4, true, true); }
-      else { if (steady) CFD_LEXW_LAUNCH(CAVITY, 4, false, false); else CFD_LEXW_LAUNCH(CAVITY, 4, true, false); }
-    } else if (ns == 1) { if (steady) CFD_LEXW_LAUNCH(CAVITY, 1, false, false); else CFD_LEXW_LAUNCH(CAVITY, 1, true, false); }
-    else if (ns == 2) { if (steady) CFD_LEXW_LAUNCH(CAVITY, 2, false, false); else CFD_LEXW_LAUNCH(CAVITY, 2, true, false); }
-    else if (sample) { if (steady) CFD_LEXW_LAUNCH(CAVITY, 3, false, true); else CFD_LEXW_LAUNCH(CAVITY, 3, true, true); }
-    else { if (steady) CFD_LEXW_LAUNCH(CAVITY, 3, false, false); else CFD_LEXW_LAUNCH(CAVITY, 3, true, false); }
-#undef CFD_LEXW_LAUNCH
+      if (steady) go(std::false_type{});
+      else go(std::true_type{});
+    });
   }
 
   // K lexicographic iterations of every cell as launches m = 0.. (half-sweeps
@@ -1476,11 +1118,8 @@ class Solver {
   // sampled cell exceeds the tolerance).
   int run_lexw(int base, int K, bool tests, int kexact, int ka0, int* kstop, int* code, bool time_steady) {
     const int ns = lexw_ns();
-    // the last half-sweep: cell (ny, nx)'s K-th update, and for the open cases
-    // the top ghost (ny+1, nx)'s K-th copy one half-sweep later (lxo_row)
-    const int Hlast = P.nx + P.ny + 2 * (K - 1) + (P.case_id != CFD_CAVITY ? 1 : 0);
-    const int nl = (Hlast - 2) / (2 * ns) + 1;  // last launch covers Hlast
-    const int kmax = lexw_offset();
+    const int nl = lexw_launches(in, ns, K);
+    const int kmax = lexw_offset(in);
     LexCtl L{lexbits, (int)(lexbits_words / LEXW_SHARDS), kmax, tolv, stop, kexact, cscr};
     // the residual of iteration k of cell (j,i) (half-sweep i+j+2(k-1)) is
     // evaluated in the launch holding half-sweep i+j+2k-1; the corner cell's
@@ -1490,26 +1129,11 @@ class Solver {
     const int m_full = (!tests || kexact >= K) ? INT32_MAX : (ns >= 3) ? (2 * kexact - 1) / (2 * ns) : 0;
     std::vector<PairPlan> plans(S.size());
     std::vector<PlanNote> notes(S.size());
-    for (size_t q = 0; q < S.size(); ++q)
-      plans[q] = multi_plan(S[q].g.wj0, S[q].g.wj1 + 1, 0, 0, resident_lexw_waves / (int)S.size(), ns,
-                            // (a wave's march steps + 9 <= 127: its iterations fit one 64-bit
-                            // mask; at 6 sweeps 90 + 2 * 13 + 1 + 9 = 126)
-                            ns >= 5 ? 90 : 96,
-                            lexw_edge_pct, lexw_twc(ns), lexw_extra(ns), false, &notes[q]);
-    // steady launches of strip q: every cell the strip's launch touches (its
-    // rows and the HALO rows on each side: i + j in [smin, smax]) active in
-    // every half-sweep of the launch and of the previous one's last
-    // (smax + 1 <= H0 <= smin + 2K - 2NS - 1, H0 = 2 + 2NS m; one strip:
-    // smin = 2, smax = nx + ny). A strip of a tall grid (ranks) runs its own
-    // steady window instead of the whole grid's, which starts only once the
-    // last row has started.
-    std::vector<int> qs0(S.size()), qs1(S.size());
-    int ms0 = 0, ms1 = INT32_MAX;  // launches steady on every strip (timed)
+    std::vector<int> qs0(S.size()), qs1(S.size());  // launches steady on strip q (lexw_steady_window)
+    int ms0 = 0, ms1 = INT32_MAX;                   // launches steady on every strip (timed)
     for (size_t q = 0; q < S.size(); ++q) {
-      const Geo& g = S[q].g;
-      const int smax = P.nx + std::min(P.ny, g.j1 + HALO), smin = 1 + std::max(1, g.j0 - HALO);
-      qs0[q] = (smax - 1 + 2 * ns - 1) / (2 * ns);
-      qs1[q] = floordiv(smin + 2 * K - 2 * ns - 3, 2 * ns);
+      plans[q] = lexw_steady_plan(in, S[q].g, resident_lexw_waves / (int)S.size(), ns, &notes[q]);
+      lexw_steady_window(in, S[q].g, ns, K, &qs0[q], &qs1[q]);
       ms0 = std::max(ms0, qs0[q]);
       ms1 = std::min(ms1, qs1[q]);
     }
@@ -1530,7 +1154,7 @@ class Solver {
             if (ka0 == 0) ka = kb = 0;
           } else {
             ka = tested + 1;
-            kb = std::min(lexw_done(m - 1, ns), K - 1);
+            kb = std::min(lexw_done(in, m - 1, ns), K - 1);
             if (ranks()) {  // (only bits OR-ed over the ranks are tested)
               if (m % LEXW_RED_EVERY == 0 && kb > reduced) {
                 lexw_reduce_bits(L, reduced + 1, kb);
@@ -1667,21 +1291,8 @@ class Solver {
     lex_set_both(-1);
     solve_tolerance();
     if (multi()) exchange(B_F, HALO - 1);
-    // bit of iteration k: k + offset; waves touch iterations from about
-    // -(nx+ny)/2 (cells not yet started) to K + (nx+ny)/2 (cells finished)
-    const size_t words = (size_t)LEXW_SHARDS * ((lexw_offset() + K + (P.nx + P.ny) / 2 + 256) / 64 + 2);
-    if (lexbits_words < words) {
-      if (lexbits) HIPC(hipFree(lexbits));
-      lexbits = nullptr;
-      HIPC(hipMalloc(&lexbits, words * sizeof(unsigned long long)));
-      lexbits_words = words;
-    }
-    if (ranks() && lexflags_n < (size_t)K + 1) {
-      if (lexflags) HIPC(hipFree(lexflags));
-      lexflags = nullptr;
-      HIPC(hipMalloc(&lexflags, ((size_t)K + 1) * sizeof(double)));
-      lexflags_n = (size_t)K + 1;
-    }
+    grow_lexbits(K);
+    if (ranks()) grow(lexflags, lexflags_n, (size_t)K + 1);
     lex_reset_tests();
     HIPC(hipEventRecord(ev_a, st));
     const int kexact = (ns < 3) ? 1 : (lex_hint > 0 && lex_hint < K) ? std::max(1, lex_hint - 64) : K;
@@ -1706,9 +1317,7 @@ class Solver {
       const int b1 = lex_replay(base, kstop);
       step_corner(pbuf(b1));  // (also the continuation's initial field: the refresh after iteration kstop)
       const double rk = final_residual(pbuf(b1));
-      double t2[2];
-      HIPC(hipMemcpy(t2, tolv, sizeof t2, hipMemcpyDeviceToHost));
-      if (!(rk > t2[0])) {  // cavity-01.cpp:635: the loop stops at kstop
+      if (!(rk > read_tol(false).tol)) {  // cavity-01.cpp:635: the loop stops at kstop
         iters = kstop;
         fin = b1;
         res = rk;
@@ -1735,21 +1344,14 @@ class Solver {
     HIPC(hipEventRecord(ev_b, st));
     // the reported residual: max-norm of the final field (cavity-01.cpp:659-677)
     if (iters == 0) {
-      double t2[2];
-      HIPC(hipMemcpyAsync(t2, tolv, sizeof t2, hipMemcpyDeviceToHost, st));
-      HIPC(hipStreamSynchronize(st));
-      res = t2[1];
+      res = read_tol(true).res0;
     } else if (res < 0.0) {
       step_corner(pbuf(fin));
       res = final_residual(pbuf(fin));
     }
     HIPC(hipEventSynchronize(ev_b));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    T.poisson_ms += ms;
-    long long owned = 0;
-    for (auto& s : S) owned += (long long)(s.g.j1 - s.g.j0 + 1) * P.nx;
-    T.poisson_cell_updates += owned * iters;
+    T.poisson_ms += elapsed_ms();
+    T.poisson_cell_updates += owned_cells() * iters;
     pcur = fin;
     lex_hint = (iters < K) ? iters : 0;
     if (out) {
@@ -1771,43 +1373,23 @@ class Solver {
     if (P.case_id == CFD_CAVITY)  // cavity-01.cpp:610-611: each solve starts from a zero field
       HIPC(hipMemsetAsync(X, 0, (size_t)s.g.nrows * pitch * sizeof(double), st));
     solve_tolerance();
-    int* d_it = stop;
-    double* d_res = total + 2;
     HIPC(hipEventRecord(ev_a, st));
     const int ce = std::max(1, P.check_every);
     const long long per_colour = ((long long)P.nx * P.ny + 1) / 2;
     const int maxc = per_colour <= 2 * SMALL_THREADS ? 2 : per_colour <= 4 * SMALL_THREADS ? 4
                    : per_colour <= 8 * SMALL_THREADS ? 8 : SMALL_MAXC;
-#define CFD_SMALL_LAUNCH(CASE)                                                                                    \
-  if (maxc == 2)                                                                                                  \
-    poisson_small_kernel<CASE, 2><<<1, SMALL_THREADS, 0, st>>>(s.g, C, X, s.b[B_F], tolv, P.max_iters, ce, d_it, d_res); \
-  else if (maxc == 4)                                                                                             \
-    poisson_small_kernel<CASE, 4><<<1, SMALL_THREADS, 0, st>>>(s.g, C, X, s.b[B_F], tolv, P.max_iters, ce, d_it, d_res); \
-  else if (maxc == 8)                                                                                             \
-    poisson_small_kernel<CASE, 8><<<1, SMALL_THREADS, 0, st>>>(s.g, C, X, s.b[B_F], tolv, P.max_iters, ce, d_it, d_res); \
-  else                                                                                                            \
-    poisson_small_kernel<CASE, SMALL_MAXC><<<1, SMALL_THREADS, 0, st>>>(s.g, C, X, s.b[B_F], tolv, P.max_iters, ce, d_it, d_res)
-    if (P.case_id == CFD_CAVITY) { CFD_SMALL_LAUNCH(CAVITY); }
-    else if (P.case_id == CFD_CHANNEL) { CFD_SMALL_LAUNCH(CHANNEL); }
-    else { CFD_SMALL_LAUNCH(BACKSTEP); }
-#undef CFD_SMALL_LAUNCH
+    with_case(P.case_id, [&](auto c) {
+      auto go = [&](auto mc) {
+        poisson_small_kernel<decltype(c)::value, decltype(mc)::value><<<1, SMALL_THREADS, 0, st>>>(
+            s.g, C, X, s.b[B_F], tolv, P.max_iters, ce, stop, total + 2);
+      };
+      if (maxc == 2) go(Tag<2>{});
+      else if (maxc == 4) go(Tag<4>{});
+      else if (maxc == 8) go(Tag<8>{});
+      else go(Tag<SMALL_MAXC>{});
+    });
     check_launch("poisson_small");
-    HIPC(hipEventRecord(ev_b, st));
-    int iters = 0;
-    double res = 0;
-    HIPC(hipMemcpyAsync(&iters, d_it, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(&res, d_res, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    T.poisson_ms += ms;
-    T.poisson_launches += 1;
-    T.poisson_sweeps += iters;
-    T.poisson_cell_updates += (long long)P.nx * P.ny * iters;
-    if (out) {
-      out->sor_iterations = iters;
-      out->residual = res;
-    }
+    finish_one_workgroup(out, true);
   }
 
   // max-norm residual of the cavity field in p buffer `bp` (cavity-01.cpp:659-677)
@@ -1815,22 +1397,19 @@ class Solver {
     if (multi()) exchange(bp, 1);
     HIPC(hipMemsetAsync(resmax, 0, RES_SHARDS * SHARD_STRIDE * sizeof(double), st));
     for (auto& s : S) {
-      if (P.case_id == CFD_CAVITY) {
-        cavity_resmax_kernel<<<pair_grid(s), 256, 0, st>>>(s.g, C, s.b[bp], s.b[B_F], resmax);
-      } else {
-        const int rows = std::min(s.g.j1, P.ny) - std::max(s.g.j0, 1) + 1;
-        const dim3 grid((P.nx + 63) / 64, std::max(1, (rows + 3) / 4));
-        if (P.case_id == CFD_CHANNEL) open_resmax_kernel<CHANNEL><<<grid, 256, 0, st>>>(s.g, C, s.b[bp], s.b[B_F], resmax);
-        else open_resmax_kernel<BACKSTEP><<<grid, 256, 0, st>>>(s.g, C, s.b[bp], s.b[B_F], resmax);
-      }
+      with_case(P.case_id, [&](auto c) {
+        if constexpr (decltype(c)::value == CAVITY) {
+          cavity_resmax_kernel<<<pair_grid(s), 256, 0, st>>>(s.g, C, s.b[bp], s.b[B_F], resmax);
+        } else {
+          const int rows = std::min(s.g.j1, P.ny) - std::max(s.g.j0, 1) + 1;
+          const dim3 grid((P.nx + 63) / 64, std::max(1, (rows + 3) / 4));
+          open_resmax_kernel<decltype(c)::value><<<grid, 256, 0, st>>>(s.g, C, s.b[bp], s.b[B_F], resmax);
+        }
+      });
       check_launch("resmax");
     }
     if (comm && comm->nranks > 1) comm_allreduce_max(comm, resmax, RES_SHARDS * SHARD_STRIDE, st);
-    HIPC(hipMemcpyAsync(h_shard, resmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    double res = 0.0;
-    for (int q = 0; q < RES_SHARDS; ++q) res = std::max(res, h_shard[q * SHARD_STRIDE]);
-    return res;
+    return shard_max(resmax, true);
   }
 
   // the reference order on a reference-sized grid in one workgroup (smlex.hip):
@@ -1848,27 +1427,10 @@ class Solver {
     if (!smlex_ck)
       HIPC(hipMalloc(&smlex_ck, smlex_ck_doubles(P.nx, P.ny) * sizeof(double)));
     solve_tolerance();
-    int* d_it = stop;
-    double* d_res = total + 2;
     HIPC(hipEventRecord(ev_a, st));
-    smlex_launch(P.case_id, s.g, C, X, s.b[B_F], tolv, P.max_iters, smlex_ck, d_it, d_res, st);
+    smlex_launch(P.case_id, s.g, C, X, s.b[B_F], tolv, P.max_iters, smlex_ck, stop, total + 2, st);
     check_launch("poisson_smlex");
-    HIPC(hipEventRecord(ev_b, st));
-    int iters = 0;
-    double res = 0;
-    HIPC(hipMemcpyAsync(&iters, d_it, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(&res, d_res, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    T.poisson_ms += ms;
-    T.poisson_launches += 1;
-    T.poisson_sweeps += iters;
-    T.poisson_cell_updates += (long long)P.nx * P.ny * iters;
-    if (out) {
-      out->sor_iterations = iters;
-      out->residual = res;
-    }
+    finish_one_workgroup(out, true);
   }
 
   // ---------------------------------------------------------- multigrid --
@@ -2094,11 +1656,7 @@ class Solver {
     HIPC(hipMemsetAsync(resmax, 0, RES_SHARDS * SHARD_STRIDE * sizeof(double), st));
     launch();
     check_launch("resmax");
-    HIPC(hipMemcpyAsync(h_shard, resmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    double res = 0.0;
-    for (int q = 0; q < RES_SHARDS; ++q) res = std::max(res, h_shard[q * SHARD_STRIDE]);
-    return res;
+    return shard_max(resmax, true);
   }
 
   // an open case's own max-norm residual, on the ghosts the buffer holds
@@ -2178,9 +1736,9 @@ class Solver {
   }
 
   void solve(cfd_step_info* out) {
-    rep = cfd_sor_plan{};  // (cfd_sor_plan_info covers this solve)
+    rep = PlanReport{};  // (cfd_sor_plan_info covers this solve)
     solve_by_engine(out);
-    rep.sor_kernel = T.sor_kernel;
+    rep.rep.sor_kernel = T.sor_kernel;
   }
 
   void solve_by_engine(cfd_step_info* out) {
@@ -2254,12 +1812,7 @@ class Solver {
   // check_every counts from the solve's start (iteration it_base + kk is
   // tested when it is a multiple of check_every). 0 outside the segments.
   int it_base = 0;
-  double tol_host() {
-    double t2[2];
-    HIPC(hipMemcpyAsync(t2, tolv, sizeof t2, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return t2[0];
-  }
+  double tol_host() { return read_tol(true).tol; }
   int res_segments = 0;  // segments of the last solve (tests: a solve from rest relaunches the resident kernel)
   void solve_resident_segments(cfd_step_info* out) {
     const int K = P.max_iters;
@@ -2362,13 +1915,7 @@ class Solver {
       HIPC(hipMemcpyAsync(s.b[B_P2], s.b[pbuf(b0)], (size_t)s.g.nrows * pitch * sizeof(double),
                           hipMemcpyDeviceToDevice, st));
     lex_set_both(B_P2);
-    const size_t words = (size_t)LEXW_SHARDS * ((lexw_offset() + w + (P.nx + P.ny) / 2 + 256) / 64 + 2);
-    if (lexbits_words < words) {
-      if (lexbits) HIPC(hipFree(lexbits));
-      lexbits = nullptr;
-      HIPC(hipMalloc(&lexbits, words * sizeof(unsigned long long)));
-      lexbits_words = words;
-    }
+    grow_lexbits(w);
     lex_reset_tests();
     HIPC(hipEventRecord(ev_a, st));
     int k2 = -1, code = 0;
@@ -2383,12 +1930,8 @@ class Solver {
     }
     HIPC(hipEventRecord(ev_b, st));
     *res = final_residual(pbuf(fin));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    T.poisson_ms += ms;
-    long long owned = 0;
-    for (auto& s : S) owned += (long long)(s.g.j1 - s.g.j0 + 1) * P.nx;
-    T.poisson_cell_updates += owned * iters;
+    T.poisson_ms += elapsed_ms();
+    T.poisson_cell_updates += owned_cells() * iters;
     pcur = fin;
     *k = iters;
     return code == 1 || !(*res > tol_host());
@@ -2405,50 +1948,10 @@ class Solver {
     const size_t fbytes = (size_t)s.g.nrows * pitch * sizeof(double);
     double* pin = s.b[pbuf(base)];
     double* pout = s.b[pbuf((base + 1) % nbufs())];
-    // the cavity starts each solve from a zero field (cavity-01.cpp:610-611),
-    // the channel from the previous pressure (channel-01.cpp:636); a later
-    // segment of the solve (solve_resident_segments) from the field reached
-    if (P.case_id == CFD_CAVITY && fresh) HIPC(hipMemsetAsync(pin, 0, fbytes, st));
-    const bool open = P.case_id == CFD_CHANNEL;
-    const int cid = open ? CHANNEL : CAVITY;
-    solve_tolerance();
-    if (!res_x[0])
-      for (auto*& x : res_x) {
-        HIPC(hipMalloc(&x, fbytes));
-        HIPC(hipMemsetAsync(x, 0, fbytes, st));  // (cells outside the grid stay finite)
-      }
-    const int ntiles = rplan.ctiles * rplan.rtiles, K = P.max_iters;
-    const size_t words = res_state_words(ntiles, K);
-    if (words > res_state_n) {
-      if (res_state) HIPC(hipFree(res_state));
-      res_state = nullptr;
-      HIPC(hipMalloc(&res_state, words * sizeof(unsigned)));
-      res_state_n = words;
-    }
-    ResCtl R{};
-    R.xa = res_x[0];
-    R.xb = res_x[1];
-    R.flags = res_state;
-    R.proven = R.flags + ntiles;
-    R.status = reinterpret_cast<int*>(R.proven + K + 1);
-    R.tol = tolv;
-    R.K = K;
-    R.check_every = std::max(1, P.check_every);
-    R.k_base = it_base;
-    HIPC(hipMemsetAsync(res_state, 0, words * sizeof(unsigned), st));
-    HIPC(hipMemsetAsync(R.status, 0xff, sizeof(int), st));  // (-1 until the launch sets its status)
-    HIPC(hipEventRecord(ev_a, st));
-    res_launch(cid, false, s.g, C, pin, pout, s.b[B_F], R, rplan, 0, st);
-    check_launch("poisson (resident)");
-    if (open) res_refresh(s.g, pout, st);  // the refresh after the last sweep (its red ghosts)
-    HIPC(hipEventRecord(ev_b, st));
-    HIPC(hipMemcpyAsync(h_stat, R.status, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
+    const int K = P.max_iters;
+    ResCtl R = res_prepare(pin, fbytes, K, fresh, false);
+    res_run(false, pin, pout, R, 0, "poisson (resident)");
     const int code = h_stat[0], kst = h_stat[1], timeout = h_stat[2];
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    T.poisson_ms += ms;
-    T.poisson_launches += 1;
     // a wait that timed out (tiles not co-resident after all): nothing but the
     // exchange fields and p_out was written, p_in is intact - the exact
     // launches take the whole solve
@@ -2459,46 +1962,92 @@ class Solver {
     }
     if (code == -1) throw Error(CFD_E_STATE, "resident SOR solve: the launch set no status");
     if (code == 0 || code == 1) {
-      const int iters = code == 0 ? K : 0;
-      double res;
-      if (iters == 0) {
-        double t2[2];
-        HIPC(hipMemcpy(t2, tolv, sizeof t2, hipMemcpyDeviceToHost));
-        res = t2[1];
-      } else {
-        pcur = (base + 1) % nbufs();
-        res = final_residual(pbuf(pcur));  // the final field's (cavity-01.cpp:659-677)
-      }
-      T.poisson_sweeps += iters;
-      T.poisson_cell_updates += (long long)P.nx * P.ny * iters;
-      if (out) {
-        out->sor_iterations = iters;
-        out->residual = res;
-      }
+      res_done(out, code, K, (base + 1) % nbufs());
       return true;
     }
     if (code != 2 || kst < 0 || kst >= K) throw Error(CFD_E_STATE, "resident SOR solve: bad status");
     ++T.proof_fallbacks;
     k0 = kst;
     if (k0 > 0) {  // the field after k0 iterations, from the solve's intact input
-      HIPC(hipMemsetAsync(res_state, 0, words * sizeof(unsigned), st));
+      HIPC(hipMemsetAsync(res_state, 0, res_state_words(rplan.ctiles * rplan.rtiles, K) * sizeof(unsigned), st));
       R.K = k0;
-      HIPC(hipEventRecord(ev_a, st));
-      res_launch(cid, false, s.g, C, pin, pout, s.b[B_F], R, rplan, RES_REPLAY, st);
-      check_launch("poisson (resident replay)");
-      if (open) res_refresh(s.g, pout, st);
-      HIPC(hipEventRecord(ev_b, st));
-      HIPC(hipMemcpyAsync(h_stat, R.status, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPC(hipStreamSynchronize(st));
-      HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-      T.poisson_ms += ms;
-      T.poisson_launches += 1;
+      res_run(false, pin, pout, R, RES_REPLAY, "poisson (resident replay)");
       if (h_stat[2]) {  // (as above: the exact launches from scratch)
         ++T.resident_timeouts;
         k0 = 0;
       }
     }
     return false;
+  }
+
+  // What both resident solves start with: the input field (the cavity starts each solve from a zero field,
+  // cavity-01.cpp:610-611; the channel from the previous pressure, channel-01.cpp:636, left intact in p_in for
+  // the exact path; a later segment, fresh = false, from the field reached), the tolerance, the exchange fields
+  // (allocated at the first solve), the zeroed state words for K iterations of every tile and the control block
+  // over them; lex: the sampled exceedance bits too
+  ResCtl res_prepare(double* pin, size_t fbytes, int K, bool fresh, bool lex) {
+    if (P.case_id == CFD_CAVITY && fresh) HIPC(hipMemsetAsync(pin, 0, fbytes, st));
+    solve_tolerance();
+    if (!res_x[0])
+      for (auto*& x : res_x) {
+        HIPC(hipMalloc(&x, fbytes));
+        HIPC(hipMemsetAsync(x, 0, fbytes, st));  // (cells outside the grid stay finite)
+      }
+    const int ntiles = rplan.ctiles * rplan.rtiles;
+    const size_t words = res_state_words(ntiles, K);
+    grow(res_state, res_state_n, words);
+    ResCtl R{};
+    R.xa = res_x[0];
+    R.xb = res_x[1];
+    R.flags = res_state;
+    R.proven = R.flags + ntiles;
+    R.status = reinterpret_cast<int*>(R.proven + K + 1);
+    R.tol = tolv;
+    R.K = K;
+    R.check_every = std::max(1, P.check_every);
+    R.k_base = it_base;  // (0 in the reference order: its segments number their iterations themselves)
+    HIPC(hipMemsetAsync(res_state, 0, words * sizeof(unsigned), st));
+    if (lex) {
+      R.bwords = res_lex_words(P.nx, P.ny, K);
+      const size_t bn = (size_t)8 * R.bwords;
+      grow(res_bits, res_bits_n, bn);
+      R.bits = res_bits;
+      R.koff = res_lex_koff(P.nx, P.ny);
+      HIPC(hipMemsetAsync(res_bits, 0, bn * sizeof(unsigned long long), st));
+    }
+    HIPC(hipMemsetAsync(R.status, 0xff, sizeof(int), st));  // (-1 until the launch sets its status)
+    return R;
+  }
+  // one resident launch (red-black channel: and the refresh after its last sweep), timed; leaves its status in h_stat
+  void res_run(bool lex, const double* pin, double* pout, const ResCtl& R, int flags, const char* what) {
+    Strip& s = S[0];
+    const bool open = P.case_id == CFD_CHANNEL;
+    HIPC(hipEventRecord(ev_a, st));
+    res_launch(open ? CHANNEL : CAVITY, lex, s.g, C, pin, pout, s.b[B_F], R, rplan, flags, st);
+    check_launch(what);
+    if (open && !lex) res_refresh(s.g, pout, st);
+    HIPC(hipEventRecord(ev_b, st));
+    HIPC(hipMemcpyAsync(h_stat, R.status, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    T.poisson_ms += elapsed_ms();
+    T.poisson_launches += 1;
+  }
+  // a resident launch that ran to the cap (code 0: the field in buffer `next`) or ran no iteration (code 1)
+  void res_done(cfd_step_info* out, int code, int K, int next) {
+    const int iters = code == 0 ? K : 0;
+    double res;
+    if (iters == 0) {
+      res = read_tol(false).res0;
+    } else {
+      pcur = next;
+      res = final_residual(pbuf(pcur));  // the final field's (cavity-01.cpp:659-677)
+    }
+    T.poisson_sweeps += iters;
+    T.poisson_cell_updates += (long long)P.nx * P.ny * iters;
+    if (out) {
+      out->sor_iterations = iters;
+      out->residual = res;
+    }
   }
 
   // The reference's order as one resident launch (resident.hip, LEX): every
@@ -2512,58 +2061,10 @@ class Solver {
     const size_t fbytes = (size_t)s.g.nrows * pitch * sizeof(double);
     double* pin = s.b[pbuf(base)];
     double* pout = s.b[pbuf(base ^ 1)];
-    // the cavity starts each solve from a zero field (cavity-01.cpp:610-611);
-    // the channel from the previous pressure (channel-01.cpp:636), left intact in
-    // p_in for the exact path; a later segment from the field reached
-    if (P.case_id == CFD_CAVITY && fresh) HIPC(hipMemsetAsync(pin, 0, fbytes, st));
-    solve_tolerance();
-    if (!res_x[0])
-      for (auto*& x : res_x) {
-        HIPC(hipMalloc(&x, fbytes));
-        HIPC(hipMemsetAsync(x, 0, fbytes, st));
-      }
-    const int ntiles = rplan.ctiles * rplan.rtiles, K = P.max_iters;
-    const size_t words = res_state_words(ntiles, K);
-    if (words > res_state_n) {
-      if (res_state) HIPC(hipFree(res_state));
-      res_state = nullptr;
-      HIPC(hipMalloc(&res_state, words * sizeof(unsigned)));
-      res_state_n = words;
-    }
-    const int bwords = res_lex_words(P.nx, P.ny, K);
-    const size_t bn = (size_t)8 * bwords;
-    if (bn > res_bits_n) {
-      if (res_bits) HIPC(hipFree(res_bits));
-      res_bits = nullptr;
-      HIPC(hipMalloc(&res_bits, bn * sizeof(unsigned long long)));
-      res_bits_n = bn;
-    }
-    ResCtl R{};
-    R.xa = res_x[0];
-    R.xb = res_x[1];
-    R.flags = res_state;
-    R.proven = R.flags + ntiles;
-    R.status = reinterpret_cast<int*>(R.proven + K + 1);
-    R.tol = tolv;
-    R.K = K;
-    R.check_every = std::max(1, P.check_every);
-    R.bits = res_bits;
-    R.bwords = bwords;
-    R.koff = res_lex_koff(P.nx, P.ny);
-    HIPC(hipMemsetAsync(res_state, 0, words * sizeof(unsigned), st));
-    HIPC(hipMemsetAsync(res_bits, 0, bn * sizeof(unsigned long long), st));
-    HIPC(hipMemsetAsync(R.status, 0xff, sizeof(int), st));  // (-1 until the launch sets its status)
-    HIPC(hipEventRecord(ev_a, st));
-    res_launch(P.case_id == CFD_CHANNEL ? CHANNEL : CAVITY, true, s.g, C, pin, pout, s.b[B_F], R, rplan, 0, st);
-    check_launch("poisson (resident, reference order)");
-    HIPC(hipEventRecord(ev_b, st));
-    HIPC(hipMemcpyAsync(h_stat, R.status, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
+    const int K = P.max_iters;
+    const ResCtl R = res_prepare(pin, fbytes, K, fresh, true);
+    res_run(true, pin, pout, R, 0, "poisson (resident, reference order)");
     const int code = h_stat[0], timeout = h_stat[2];
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
-    T.poisson_ms += ms;
-    T.poisson_launches += 1;
     if (timeout) {  // (tiles not co-resident after all: p_in is intact, the exact path takes the solve)
       ++T.resident_timeouts;
       return false;
@@ -2574,23 +2075,8 @@ class Solver {
       return false;
     }
     if (code != 0 && code != 1) throw Error(CFD_E_STATE, "resident SOR solve: bad status");
-    const int iters = code == 0 ? K : 0;
-    double res;
-    if (iters == 0) {
-      double t2[2];
-      HIPC(hipMemcpy(t2, tolv, sizeof t2, hipMemcpyDeviceToHost));
-      res = t2[1];
-      pcur = base;
-    } else {
-      pcur = base ^ 1;
-      res = final_residual(pbuf(pcur));  // the final field's (cavity-01.cpp:659-677)
-    }
-    T.poisson_sweeps += iters;
-    T.poisson_cell_updates += (long long)P.nx * P.ny * iters;
-    if (out) {
-      out->sor_iterations = iters;
-      out->residual = res;
-    }
+    pcur = base;
+    res_done(out, code, K, base ^ 1);
     return true;
   }
 
@@ -2691,18 +2177,14 @@ class Solver {
       // reference's while condition, cavity-01.cpp:633)
       if (code == 0 && last_tested < P.max_iters - 1) {
         HIPC(hipStreamSynchronize(st));
-        double t2[2];
-        HIPC(hipMemcpy(t2, tolv, sizeof t2, hipMemcpyDeviceToHost));
+        const Tol t2 = read_tol(false);
         for (int kk = last_tested + 1; kk <= P.max_iters - 1; ++kk) {
           double r;
           bool pr = false;
           if (kk == 0) {
-            r = t2[1];
+            r = t2.res0;
           } else if ((it_base + kk) % P.check_every == 0) {
-            const double* slot = ring + (size_t)(kk & (RING - 1)) * RES_SHARDS * SHARD_STRIDE;
-            HIPC(hipMemcpy(h_shard, slot, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost));
-            r = 0.0;
-            for (int q = 0; q < RES_SHARDS; ++q) r = std::max(r, h_shard[q * SHARD_STRIDE]);
+            r = shard_max(ring + (size_t)(kk & (RING - 1)) * RES_SHARDS * SHARD_STRIDE, false);
             pr = launches[launch_of(kk)].proof;
           } else {
             continue;
@@ -2712,7 +2194,7 @@ class Solver {
               open_k = kk;
               break;
             }
-          } else if (!(r > t2[0])) {
+          } else if (!(r > t2.tol)) {
             iters = kk;
             break;
           }
@@ -2738,8 +2220,7 @@ class Solver {
     proof_launch = window_proof = false;
     HIPC(hipEventRecord(ev_b, st));
     HIPC(hipEventSynchronize(ev_b));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_a, ev_b));
+    float ms = elapsed_ms();
     // the launch that computed iteration `iters`; if it ran further, redo the
     // first r of its iterations from its (intact) input into its output buffer
     int last = -1, replayed = 0;
@@ -2758,9 +2239,7 @@ class Solver {
         poisson_launch(last, launches[last].first, r, base, 1, 0, true);
         HIPC(hipEventRecord(ev_b, st));
         HIPC(hipEventSynchronize(ev_b));
-        float ms2 = 0.f;
-        HIPC(hipEventElapsedTime(&ms2, ev_a, ev_b));
-        ms += ms2;
+        ms += elapsed_ms();
         replayed = r;
       }
     }
@@ -2770,23 +2249,16 @@ class Solver {
     T.poisson_sweeps += work_sweeps + replayed;
     T.poisson_overlapped += n_overlapped;
     n_overlapped = 0;
-    long long owned = 0;
-    for (auto& s : S) owned += (long long)(s.g.j1 - s.g.j0 + 1) * P.nx;
-    T.poisson_cell_updates += owned * iters;
+    T.poisson_cell_updates += owned_cells() * iters;
     double res;
     if (iters == 0) {
-      double t2[2];
-      HIPC(hipMemcpy(t2, tolv, sizeof t2, hipMemcpyDeviceToHost));
-      res = t2[1];
+      res = read_tol(false).res0;
     } else if (launches[last].proof) {
       // a proof-mode launch computed the last iteration (the cap): the
       // reported residual is the final field's (cavity-01.cpp:659-677)
       res = final_residual(pbuf((base + last + 1) % nbufs()));
     } else {
-      const double* slot = ring + (size_t)(iters & (RING - 1)) * RES_SHARDS * SHARD_STRIDE;
-      HIPC(hipMemcpy(h_shard, slot, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost));
-      res = 0.0;
-      for (int q = 0; q < RES_SHARDS; ++q) res = std::max(res, h_shard[q * SHARD_STRIDE]);
+      res = shard_max(ring + (size_t)(iters & (RING - 1)) * RES_SHARDS * SHARD_STRIDE, false);
     }
     // launch m's output is buffer (base+m+1) mod nbufs (the replay writes there too)
     pcur = (base + last + 1) % nbufs();
@@ -2860,11 +2332,8 @@ class Solver {
       comm_allreduce_max(comm, divmax, RES_SHARDS * SHARD_STRIDE, st);
     }
     double ke = 0;
-    HIPC(hipMemcpyAsync(h_shard, divmax, RES_SHARDS * SHARD_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(&ke, total + 1, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    double md = 0;
-    for (int q = 0; q < RES_SHARDS; ++q) md = std::max(md, h_shard[q * SHARD_STRIDE]);
+    const double md = shard_max(divmax, true);  // (waits for the stream: ke has arrived too)
     if (out) {
       out->max_divergence = md;
       out->avg_kinetic_energy = ke / fluid_count;
@@ -3176,7 +2645,7 @@ int cfd_set_tuning(cfd_solver* s, int knob, int value) { return guard([&] { S_(s
 int cfd_sor_plan_info(cfd_solver* s, cfd_sor_plan* out) {
   return guard([&] {
     if (!out) throw Error(CFD_E_ARG, "null output");
-    *out = S_(s)->rep;
+    *out = S_(s)->rep.rep;
   });
 }
 

@@ -392,10 +392,10 @@ int cfd_set_tuning(cfd_solver* s, int knob, int value);
  * order first launched, with the number of launches that ran it.
  */
 enum cfd_sor_plan_kind {
-  CFD_PLAN_PAIR = 0,     /* red-black fused launch of 2 - 4 sweeps (Solver::multi_plan) */
-  CFD_PLAN_WAVE = 1,     /* red-black one-sweep launch (Solver::wave_bands): no boundary class (the = th),
+  CFD_PLAN_PAIR = 0,     /* red-black fused launch of 2 - 4 sweeps (csrc/plan.hpp multi_plan) */
+  CFD_PLAN_WAVE = 1,     /* red-black one-sweep launch (plan.hpp wave_bands): no boundary class (the = th),
                             no 10-row groups (extra 0) */
-  CFD_PLAN_LEXW = 2,     /* reference order: the steady plan (multi_plan); the ramp launches tile by their own
+  CFD_PLAN_LEXW = 2,     /* reference order: the steady plan (lexw_steady_plan); the ramp launches tile by their own
                             heights, reported in cfd_sor_plan */
   CFD_PLAN_INTERIOR = 3  /* red-black ranks with halo overlap: the interior rows of a fused launch, planned for
                             the budget less the two boundary launches' tiles (those are fixed 16-row bands and

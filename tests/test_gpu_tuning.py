@@ -9,8 +9,8 @@ poisson_sweeps (knobs move tiles, not launches). There are no tolerances in this
 The plan report (cfd_sor_plan_info, Solver.sor_plan()) keeps the cases from being vacuous: a case
 chosen for a plan shape asserts that shape from the report, and every plan of every case is held to
 the planner's invariants (check_plan). The knobs bring the plan regimes of the BASELINE sizes within
-reach of grids of ~10^5 cells; the shapes below were read off Solver::multi_plan / wave_bands /
-launch_lexw for an MI355X (256 CUs: budgets of 2048 tiles) and are asserted, not assumed.
+reach of grids of ~10^5 cells; the shapes below were read off csrc/plan.hpp (multi_plan, wave_bands,
+lexw_launch_plan) for an MI355X (256 CUs: budgets of 2048 tiles) and are asserted, not assumed.
 
 Fixtures (grid, cap; what the report shows there):
   lex cavity 460 x 188, K 420 (2K > nx + ny: steady launches; 5 column tiles of 110 columns, two wall
@@ -33,7 +33,7 @@ Fixtures (grid, cap; what the report shows there):
       1000: one band per column tile; pair_edge_pct 10: the 8; both march orders.
   rb cavity fixture "A" of tests/check_every_cases.py (240 x 120, natural stop at 341): with the proof
       on, the fallback window.
-  rb cavity 460 x 188, K 61 = 15 x 4 + 1: the last launch is poisson_wave_kernel under wave_bands.
+  rb cavity 460 x 188, K 61 = 15 x 4 + 1: the last launch is poisson_wave_kernel under plan.hpp's wave_bands.
   rb cavity 700 x 150, K 61: 7 column tiles x 152 rows exceed pair_wps 1's budget of 1024 at one-row
       bands - the knob that brings a budget-bound red-black plan within reach at this size.
   rb channel 460 x 152 and step 480 x 160, K 420: proof on (open.hip, the step's left class) and off
@@ -239,6 +239,17 @@ RB_COMBOS = [{"pair_wps": 1, "pair_edge_pct": 10, "march_min_th": 1}, {"pair_wps
 RB_ALL = RB_SINGLES + RB_COMBOS
 RB_PAIR = [s for s in RB_ALL if "wave_wps" not in s]  # (fixtures without a one-sweep launch)
 RB_SOME = [{"pair_wps": 1}, {"pair_edge_pct": 10}, {"march_min_th": 1}, {"march_min_th": 1000}, {"march_order": 1}] + RB_COMBOS
+# per test (scripts/record_sor_plans.py records the plans of the same lists)
+LEX_STEP = [{}, {"lexw_left": 0}, {"lexw_left": 1}] + LEX_ALL
+LEX_TALL = [{}, {"lexw_waves": 64}, {"march_min_th": 1}, {"march_min_th": 7}, {"lexw_ramp_pct": 50}, {"lexw_edge_pct": 10}] + LEX_COMBOS
+LEX_STRIPS = [{}, {"lexw_waves": 64}, {"march_min_th": 1}, {"march_min_th": 1000}, {"lexw_edge_pct": 10}, {"lexw_ramp_pct": 100},
+              {"lexw_updown": 0}, LEX_COMBOS[2]]
+LEX_DEEP = [{}, {"march_min_th": 1}, {"lexw_edge_pct": 10}, {"lexw_waves": 64}, {"lexw_updown": 0}]
+RB_REMAINDER = [{}, {"wave_wps": 1}, {"wave_wps": 4}, {"march_min_th": 1}, {"march_min_th": 7}, {"march_min_th": 1000}, {"march_order": 1}]
+RB_WIDE = [{"march_min_th": 1}, {"pair_wps": 1, "march_min_th": 1}, RB_COMBOS[0]]
+RB_OPEN_EXACT = [{}, {"pair_wps": 1}, {"pair_edge_pct": 10}, {"march_min_th": 1}, {"march_min_th": 1000}, {"march_order": 1}]
+RB_RANKS = [{}, {"pair_wps": 1}, {"pair_wps": 4}, {"march_min_th": 1}, {"march_min_th": 1000}, {"pair_edge_pct": 10}, {"march_order": 1},
+            RB_COMBOS[0]]
 
 
 def lex_regimes(setting, b, rep, max_th=96, up_exact=True, ramp_default=0):
@@ -337,7 +348,7 @@ def test_lex_channel(setting):
         assert b.up_bands >= 1
 
 
-@pytest.mark.parametrize("setting", [{}, {"lexw_left": 0}, {"lexw_left": 1}] + LEX_ALL, ids=ident)
+@pytest.mark.parametrize("setting", LEX_STEP, ids=ident)
 def test_lex_step(setting):
     """Backwards step 480 x 160 with the step's column at 240 and the inlet 80 rows high, capped at 420: of
     the five 110-column tiles, tile 1 is in the left class (beside the wall tile), tile 2 crosses the
@@ -356,8 +367,7 @@ def test_lex_step(setting):
     assert b.launch_tiles == 2 * b.nbe0 + (b.ctiles - 2) * b.nb0 + b.xn * b.xbn * 2  # (crossing bands in three parts)
 
 
-@pytest.mark.parametrize("setting", [{}, {"lexw_waves": 64}, {"march_min_th": 1}, {"march_min_th": 7},
-                                     {"lexw_ramp_pct": 50}, {"lexw_edge_pct": 10}] + LEX_COMBOS, ids=ident)
+@pytest.mark.parametrize("setting", LEX_TALL, ids=ident)
 def test_lex_tall(setting):
     """Cavity 129 x 300 capped at 60 (all ramp): a ramp launch at height 1 has more than 256 bands, so the
     band-table rule raises it by 10; with march_min_th 1 the steady height is 1, the raised height lies
@@ -372,9 +382,7 @@ def test_lex_tall(setting):
         assert b.th == 1 and rep.ramp_fallback > 0 and rep.ramp_th_max == 2
 
 
-@pytest.mark.parametrize("setting", [{}, {"lexw_waves": 64}, {"march_min_th": 1}, {"march_min_th": 1000},
-                                     {"lexw_edge_pct": 10}, {"lexw_ramp_pct": 100}, {"lexw_updown": 0},
-                                     LEX_COMBOS[2]], ids=ident)
+@pytest.mark.parametrize("setting", LEX_STRIPS, ids=ident)
 def test_lex_cavity_strips(setting):
     """The cavity fixture on 3 strips: 3 sweeps per launch (112-column tiles), one plan per strip, each
     for a third of the budget (lexw_waves 64: 21 tiles)."""
@@ -387,8 +395,7 @@ def test_lex_cavity_strips(setting):
 
 
 @pytest.mark.parametrize("spl", [5, 6])
-@pytest.mark.parametrize("setting", [{}, {"march_min_th": 1}, {"lexw_edge_pct": 10}, {"lexw_waves": 64},
-                                     {"lexw_updown": 0}], ids=ident)
+@pytest.mark.parametrize("setting", LEX_DEEP, ids=ident)
 def test_lex_cavity_deep_launches(spl, setting):
     """The cavity fixture at 5 and 6 sweeps per launch: the LDS source ring, 106- / 102-column tiles
     (5 of them), max_th 90."""
@@ -457,11 +464,10 @@ def test_rb_cavity_converging(setting):
         rb_regimes(setting, b)
 
 
-@pytest.mark.parametrize("setting", [{}, {"wave_wps": 1}, {"wave_wps": 4}, {"march_min_th": 1}, {"march_min_th": 7},
-                                     {"march_min_th": 1000}, {"march_order": 1}], ids=ident)
+@pytest.mark.parametrize("setting", RB_REMAINDER, ids=ident)
 def test_rb_cavity_one_sweep_last_launch(setting):
     """The cavity fixture capped at 61 = 15 x 4 + 1: the last launch runs one iteration with
-    poisson_wave_kernel under wave_bands (120-column tiles: 4 of them); march_min_th 1 gives it one-row
+    poisson_wave_kernel under plan.hpp's wave_bands (120-column tiles: 4 of them); march_min_th 1 gives it one-row
     bands, 1000 one band per column tile."""
     t, rep = check("rb_remainder", setting, "march")
     (w,) = one(rep, WAVE)
@@ -478,7 +484,7 @@ def test_rb_cavity_one_sweep_last_launch(setting):
         assert w.nb0 == 1 and w.th == rows
 
 
-@pytest.mark.parametrize("setting", [{"march_min_th": 1}, {"pair_wps": 1, "march_min_th": 1}, RB_COMBOS[0]], ids=ident)
+@pytest.mark.parametrize("setting", RB_WIDE, ids=ident)
 def test_rb_cavity_wide_budget_bound(setting):
     """Cavity 700 x 150 capped at 61: at one-row bands 7 column tiles x 152 rows are more tiles than
     pair_wps 1's round (1024 on 256 CUs), so the budget, not the floor, sets the band count - the plan
@@ -505,8 +511,7 @@ def test_rb_open_proof(case, setting):
 
 
 @pytest.mark.parametrize("case", ["channel", "step"])
-@pytest.mark.parametrize("setting", [{}, {"pair_wps": 1}, {"pair_edge_pct": 10}, {"march_min_th": 1},
-                                     {"march_min_th": 1000}, {"march_order": 1}], ids=ident)
+@pytest.mark.parametrize("setting", RB_OPEN_EXACT, ids=ident)
 def test_rb_open_exact(case, setting):
     """The same fixtures with proof_test off: the 2-sweep pair kernel, 210 launches."""
     t, rep = check(f"rb_{case}_exact", setting, "march")
@@ -518,13 +523,16 @@ def test_rb_open_exact(case, setting):
 _ranks_oracle = {}
 
 
-@pytest.mark.parametrize("setting", [{}, {"pair_wps": 1}, {"pair_wps": 4}, {"march_min_th": 1}, {"march_min_th": 1000},
-                                     {"pair_edge_pct": 10}, {"march_order": 1}, RB_COMBOS[0]], ids=ident)
+def ranks_params():
+    return C.make_params("cavity", nx=240, ny=128, max_iters=200)
+
+
+@pytest.mark.parametrize("setting", RB_RANKS, ids=ident)
 def test_rb_ranks_overlapped(setting):
     """Cavity 240 x 128 on two loopback ranks of 64 rows, two steps capped at 200, against the red-black
     oracle's steps: the overlapped path, whose interior rows (48 of them: 16 go to the boundary launch)
     are planned for the budget less the boundary launches' 2 x 3 tiles."""
-    cp = C.make_params("cavity", nx=240, ny=128, max_iters=200)
+    cp = ranks_params()
     if not _ranks_oracle:
         o = O.Oracle(cp, ordering=O.RB)
         _ranks_oracle["its"] = [o.step() for _ in range(2)]
