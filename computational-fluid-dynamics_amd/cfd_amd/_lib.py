@@ -53,7 +53,8 @@ SOR_KERNEL = {0: "none", 1: "march", 2: "tile", 3: "small", 4: "lexw", 5: "lex",
               8: "multigrid"}  # enum cfd_sor_kernel
 
 
-POISSON = {"sor": 0, "multigrid": 1, "multigrid-open": 2, "multigrid-step": 3, "multigrid-any": 4}  # enum cfd_poisson_method
+POISSON = {"sor": 0, "multigrid": 1, "multigrid-open": 2, "multigrid-step": 3, "multigrid-any": 4,
+           "multigrid-open-any": 5}  # enum cfd_poisson_method
 
 
 class MgOptions(ctypes.Structure):
@@ -155,6 +156,8 @@ SIGNATURES = {
     "cfd_mg_step_plan": (_i, [ctypes.POINTER(CfdParams), _ip, _ip, _ip]),
     "cfd_mg_any_plan": (_i, [ctypes.POINTER(CfdParams), _ip, _ip, _ip]),
     "cfd_mg_any_level": (_i, [ctypes.POINTER(CfdParams), _i, ctypes.POINTER(ctypes.c_double), _i]),
+    "cfd_mg_open_any_plan": (_i, [ctypes.POINTER(CfdParams), _ip, _ip, _ip]),
+    "cfd_mg_open_any_level": (_i, [ctypes.POINTER(CfdParams), _i, ctypes.POINTER(ctypes.c_double), _i]),
     "cfd_comm_unique_id": (_i, [ctypes.POINTER(ctypes.c_ubyte)]),
     "cfd_comm_init": (_vp, [ctypes.POINTER(ctypes.c_ubyte), _i, _i, _i]),
     "cfd_comm_destroy": (_i, [_vp]),

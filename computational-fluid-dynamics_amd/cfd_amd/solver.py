@@ -56,7 +56,8 @@ class _SolverBase:
         the reference's tolerance: the cavity and Rayleigh-Benard on one strip, no ranks;
         see set_poisson_method) or "multigrid-open" (the channel's multigrid solve, one
         strip, no ranks) or "multigrid-step" (the backwards-facing step's, likewise) or
-        "multigrid-any" (the cavity and Rayleigh-Benard at any grid size, likewise).
+        "multigrid-any" (the cavity and Rayleigh-Benard at any grid size, likewise) or
+        "multigrid-open-any" (the channel at any grid size, likewise).
         mg_options: pre_sweeps / post_sweeps / max_cycles."""
         self.params = params if params is not None else make_params(self.CASE)
         if self.params.case_id != self.CASE:
@@ -108,7 +109,10 @@ class _SolverBase:
         plans: mg_step_plan). "multigrid-any" is the cavity's and Rayleigh-Benard's at any
         grid whose smaller side is at least 8 (sizes halved rounding up, the last cell of a
         level as wide as what is left up to the wall; where "multigrid" has the same plan,
-        its bits; the channel and the step are refused; plans: mg_any_plan)."""
+        its bits; the channel and the step are refused; plans: mg_any_plan).
+        "multigrid-open-any" is the channel's at any grid size ("multigrid-open" with sizes
+        halved rounding up while they are at least 8; where "multigrid-open" has the same
+        plan, its bits; every other case is refused; plans: mg_open_any_plan)."""
         if method not in _lib.POISSON:
             raise ValueError(f"poisson must be one of {sorted(_lib.POISSON)}, got {method!r}")
         opt = mg_options or {}
@@ -365,6 +369,21 @@ def mg_any_level(params: CaseParams, level: int) -> list[float]:
     cp = to_cparams(params)
     out = (ctypes.c_double * 72)()
     _lib.check(_lib.lib().cfd_mg_any_level(ctypes.byref(cp), level, out, 72), "cfd_mg_any_level")
+    return list(out)
+
+
+def mg_open_any_plan(params: CaseParams) -> list[tuple[int, int]]:
+    """cfd_mg_open_any_plan (host only): [(nx, ny)] of every level of the channel's any-size
+    multigrid plan of these parameters; raises CfdError naming the rule where there is none."""
+    return _mg_level_sizes("cfd_mg_open_any_plan", params)
+
+
+def mg_open_any_level(params: CaseParams, level: int) -> list[float]:
+    """cfd_mg_open_any_level (host only): every constant of one level of the channel's
+    any-size plan, in the order include/cfd_amd.h lists."""
+    cp = to_cparams(params)
+    out = (ctypes.c_double * 75)()
+    _lib.check(_lib.lib().cfd_mg_open_any_level(ctypes.byref(cp), level, out, 75), "cfd_mg_open_any_level")
     return list(out)
 
 

@@ -18,10 +18,10 @@
 // Every kernel is one template over a scheme: a struct of static per-cell
 // functions over its level type (mg.hpp) - the update of a cell, the coarse
 // source of a coarse cell, the correction of a fine cell, whether a cell is an
-// unknown. The file states the four schemes' cell functions first (the
+// unknown. The file states the five schemes' cell functions first (the
 // cavity's mg_*, the channel's mgo_*, the step's mgs_*, the any-size cavity's
-// mga_*, each in the operand order of its restatement under tests/), then the
-// kernels, then the launches.
+// mga_*, the any-size channel's mgoa_*, each in the operand order of its
+// restatement under tests/), then the kernels, then the launches.
 // What only the step needs - the fluid tests and the coupled pair A / B - sits
 // behind `if constexpr (S::has_pair)` or folds away with S::unknown.
 // The library builds with -ffp-contract=off: no fused multiply-adds.
@@ -118,7 +118,7 @@ __device__ __forceinline__ double mg_corr(const MgLevel* Lc, const double* e, in
   return (((9.0 * c + 3.0 * V) + 3.0 * H) + D) * 0.0625;
 }
 
-// What a scheme supplies to the kernels (the other two below alike). A field is a pointer with rows of P
+// What a scheme supplies to the kernels (the others below alike). A field is a pointer with rows of P
 // doubles, global memory or LDS.
 struct MgCavity {
   using Level = MgLevel;
@@ -530,11 +530,158 @@ struct MgAny {
   }
 };
 
+// ================================================== the channel, any size ==
+// The fifth scheme (mg.hpp "the channel at any size", tests/mg_open_any_reference.py):
+// the channel's operator with the coefficients of the face between a direction's
+// last two cells and of column nx's east zero, and the transfers' weights at a
+// halved direction's end. A plain cell - west, east, south and north all with
+// the level's cx / cy - is told by four compares against the level's x.lim /
+// y.lim (the irregular flag is folded into them) and takes the channel's
+// expressions without a class or a select; a coarse cell or a fine cell that
+// takes none of the weights takes the channel's transfer.
+
+__device__ __forceinline__ bool mgoa_plain(const MgoaLevel* L, int j, int i) {
+  return i > 1 && i < L->x.lim && j > 1 && j < L->y.lim;
+}
+
+// the classes of a cell that is not plain, and the sum's terms over the neighbours that exist
+struct MgoaCell {
+  int kx, ky;
+  double cw, ce, cs, cn;
+};
+__device__ __forceinline__ MgoaCell mgoa_cell(const MgoaLevel* L, int j, int i) {
+  MgoaCell k;
+  k.kx = i == 1 ? 0 : i == L->nx ? 3 : i == L->nx - 1 ? 2 : 1;
+  k.ky = j == 1 ? 0 : j == L->ny ? 3 : j == L->ny - 1 ? 2 : 1;
+  k.cw = k.kx == 3 ? L->x.c_hi : L->cx;
+  k.ce = k.kx == 2 ? L->x.c_lo : L->cx;
+  k.cs = k.ky == 3 ? L->y.c_hi : L->cy;
+  k.cn = k.ky == 2 ? L->y.c_lo : L->cy;
+  return k;
+}
+
+// (ce pE + cw pW) + (cn pN + cs pS) over the neighbours that exist (the east zero of column nx adds nothing)
+__device__ __forceinline__ double mgoa_sum(const MgoaCell& k, double pW, double pE, double pS, double pN) {
+  const double tE = k.kx != 3 ? k.ce * pE : 0.0;
+  const double tW = k.kx != 0 ? k.cw * pW : 0.0;
+  const double tN = k.ky != 3 ? k.cn * pN : 0.0;
+  const double tS = k.ky != 0 ? k.cs * pS : 0.0;
+  return (tE + tW) + (tN + tS);
+}
+
+__device__ __forceinline__ double mgoa_relax(const MgoaLevel* L, int j, int i, double pW, double pE, double pS, double pN,
+                                             double f) {
+  if (mgoa_plain(L, j, i)) return L->rdiag[5] * (((L->cx * pE + L->cx * pW) + (L->cy * pN + L->cy * pS)) - f);
+  const MgoaCell k = mgoa_cell(L, j, i);
+  return L->rdiag[k.kx | k.ky << 2] * (mgoa_sum(k, pW, pE, pS, pN) - f);
+}
+
+__device__ __forceinline__ double mgoa_sor(const MgoaLevel* L, int j, int i, double pc, double pW, double pE, double pS,
+                                           double pN, double f) {
+  const MgoaCell k = mgoa_cell(L, j, i);
+  return pc * L->one_m_omega + L->omr[k.kx | k.ky << 2] * (mgoa_sum(k, pW, pE, pS, pN) - f);
+}
+
+// residual of fine cell (j, i), 1 <= j <= ny and 1 <= i <= nx, from fields with rows of P doubles:
+// (ce (pE - c) + cw (pW - c)) + (cn (pN - c) + cs (pS - c)) - f; column nx: cE (0 - c) for its east term
+__device__ __forceinline__ double mgoa_resid_at(const MgoaLevel* L, const double* p, const double* f, size_t P, int j,
+                                                int i) {
+  const size_t o = (size_t)j * P + i;
+  const double c = p[o], pW = p[o - 1], pE = p[o + 1], pS = p[o - P], pN = p[o + P];
+  if (mgoa_plain(L, j, i)) return ((L->cx * (pE - c) + L->cx * (pW - c)) + (L->cy * (pN - c) + L->cy * (pS - c))) - f[o];
+  const MgoaCell k = mgoa_cell(L, j, i);
+  const double tE = k.kx != 3 ? k.ce * (pE - c) : L->cE * (0.0 - c);
+  const double tW = k.kx != 0 ? k.cw * (pW - c) : 0.0;
+  const double tN = k.ky != 3 ? k.cn * (pN - c) : 0.0;
+  const double tS = k.ky != 0 ? k.cs * (pS - c) : 0.0;
+  return ((tE + tW) + (tN + tS)) - f[o];
+}
+
+// Coarse source of cell (J, I): the channel's three kinds; a cell in the last coarse column of an irregular
+// halved x and / or the last coarse row of an irregular halved y: -(b0 hS + b1 hN), hS = a0 rSW + a1 rSE and
+// hN alike, where a direction's single child, and a direction the transfer does not halve, stand alone.
+// Only children inside the grid are read.
+__device__ __forceinline__ double mgoa_restrict_cell(const MgoaLevel* Lf, const double* p, const double* f, size_t P, int J,
+                                                     int I) {
+  const int kind = Lf->kind;
+  const bool lx = I == Lf->x.last, ly = J == Lf->y.last;  // (last 0: no such cell)
+  if (lx || ly) {
+    const int j = kind == MGO_X ? J : 2 * J - 1, i = kind == MGO_Y ? I : 2 * I - 1;
+    const bool sx = kind == MGO_Y || (lx && Lf->x.single), sy = kind == MGO_X || (ly && Lf->y.single);
+    const double a0 = lx ? Lf->x.r0 : 0.5, a1 = lx ? Lf->x.r1 : 0.5;
+    const double b0 = ly ? Lf->y.r0 : 0.5, b1 = ly ? Lf->y.r1 : 0.5;
+    double hS = mgoa_resid_at(Lf, p, f, P, j, i);
+    if (!sx) hS = a0 * hS + a1 * mgoa_resid_at(Lf, p, f, P, j, i + 1);
+    if (sy) return -hS;
+    double hN = mgoa_resid_at(Lf, p, f, P, j + 1, i);
+    if (!sx) hN = a0 * hN + a1 * mgoa_resid_at(Lf, p, f, P, j + 1, i + 1);
+    return -(b0 * hS + b1 * hN);
+  }
+  if (kind == MGO_X) {
+    const double rW = mgoa_resid_at(Lf, p, f, P, J, 2 * I - 1), rE = mgoa_resid_at(Lf, p, f, P, J, 2 * I);
+    return -0.5 * (rW + rE);
+  }
+  if (kind == MGO_Y) {
+    const double rS = mgoa_resid_at(Lf, p, f, P, 2 * J - 1, I), rN = mgoa_resid_at(Lf, p, f, P, 2 * J, I);
+    return -0.5 * (rS + rN);
+  }
+  const int j = 2 * J - 1, i = 2 * I - 1;
+  const double rSW = mgoa_resid_at(Lf, p, f, P, j, i), rSE = mgoa_resid_at(Lf, p, f, P, j, i + 1);
+  const double rNW = mgoa_resid_at(Lf, p, f, P, j + 1, i), rNE = mgoa_resid_at(Lf, p, f, P, j + 1, i + 1);
+  return -0.25 * ((rSW + rSE) + (rNW + rNE));
+}
+
+// correction of fine cell (j, i): the channel's, but where i >= x.first or j >= y.first (n + 1 in a direction
+// that is regular or not halved): ay (ax c + bx H) + by (ax V + bx D) for a full transfer, ax c + bx H or
+// ay c + by V along the one halved direction, with the directions' weights (3/4, 1/4 in a regular one); b = 0
+// drops its term and leaves a times the other. The neighbours come through the channel's ghost layer.
+__device__ __forceinline__ double mgoa_corr(const MgoaLevel* L, const double* e, int pitch, int j, int i) {
+  const MgoLevel* Lc = L + 1;
+  const int kind = L->kind;
+  const int kx = i - L->x.first, ky = j - L->y.first;
+  if (kx < 0 && ky < 0) return mgo_corr(Lc, kind, e, pitch, j, i);
+  const double ax = kx < 0 ? 0.75 : L->x.pa[kx], bx = kx < 0 ? 0.25 : L->x.pb[kx];
+  const double ay = ky < 0 ? 0.75 : L->y.pa[ky], by = ky < 0 ? 0.25 : L->y.pb[ky];
+  const int J = kind == MGO_X ? j : (j + 1) >> 1, I = kind == MGO_Y ? i : (i + 1) >> 1;
+  const int dj = (j & 1) ? -1 : 1, di = (i & 1) ? -1 : 1;
+  const double c = e[(size_t)J * pitch + I];
+  if (kind == MGO_X) return bx != 0.0 ? ax * c + bx * mgo_ext(Lc, e, pitch, J, I + di) : ax * c;
+  if (kind == MGO_Y) return by != 0.0 ? ay * c + by * mgo_ext(Lc, e, pitch, J + dj, I) : ay * c;
+  const double rc = bx != 0.0 ? ax * c + bx * mgo_ext(Lc, e, pitch, J, I + di) : ax * c;
+  if (by == 0.0) return ay * rc;
+  const double V = mgo_ext(Lc, e, pitch, J + dj, I);
+  const double rv = bx != 0.0 ? ax * V + bx * mgo_ext(Lc, e, pitch, J + dj, I + di) : ax * V;
+  return ay * rc + by * rv;
+}
+
+struct MgChannelAny {
+  using Level = MgoaLevel;
+  static constexpr bool has_pair = false;
+  static constexpr bool pair_loads = true;
+  static __device__ __forceinline__ bool unknown(const Level*, int, int) { return true; }
+  static __device__ __forceinline__ double relax(const Level* L, int j, int i, double pW, double pE, double pS, double pN,
+                                                 double f) {
+    return mgoa_relax(L, j, i, pW, pE, pS, pN, f);
+  }
+  static __device__ __forceinline__ double update(const Level* L, const double* p, int P, int j, int i, double f, bool sor) {
+    return sor ? mgoa_sor(L, j, i, p[0], p[-1], p[1], p[-P], p[P], f) : mgoa_relax(L, j, i, p[-1], p[1], p[-P], p[P], f);
+  }
+  template <bool Aligned>
+  static __device__ __forceinline__ double coarse_source(const Level* Lf, const double* p, const double* f, size_t P, int J,
+                                                         int I) {
+    return mgoa_restrict_cell(Lf, p, f, P, J, I);
+  }
+  static __device__ __forceinline__ double corr(const Level* L, const double* e, int pitch, int j, int i) {
+    return mgoa_corr(L, e, pitch, j, i);
+  }
+};
+
 template <class Level> struct MgSchemeOf;
 template <> struct MgSchemeOf<MgLevel> { using type = MgCavity; };
 template <> struct MgSchemeOf<MgoLevel> { using type = MgChannel; };
 template <> struct MgSchemeOf<MgsLevel> { using type = MgStep; };
 template <> struct MgSchemeOf<MgaLevel> { using type = MgAny; };
+template <> struct MgSchemeOf<MgoaLevel> { using type = MgChannelAny; };
 
 // ============================================================ the kernels ==
 
@@ -904,6 +1051,7 @@ MG_INSTANTIATE(MgLevel)
 MG_INSTANTIATE(MgoLevel)
 MG_INSTANTIATE(MgsLevel)
 MG_INSTANTIATE(MgaLevel)
+MG_INSTANTIATE(MgoaLevel)
 #undef MG_INSTANTIATE
 
 void mgs_refresh_launch(const MgsLevel& L, double* cur, const double* prev, const double* own, void* stream) {

@@ -2,12 +2,13 @@
 // plans (host only, params.cpp) and the launches of mg.hip. No HIP types here,
 // so host-only code may include it (streams travel as void*, like comm.hip's).
 //
-// One set of kernels and one cycle serve four schemes, each an operator with
+// One set of kernels and one cycle serve five schemes, each an operator with
 // its level type and its plan:
 //   the cavity and Rayleigh-Benard (CFD_POISSON_MULTIGRID, MgLevel),
 //   the channel (CFD_POISSON_MULTIGRID_OPEN, MgoLevel),
 //   the backwards-facing step (CFD_POISSON_MULTIGRID_STEP, MgsLevel),
-//   the cavity and Rayleigh-Benard at any grid size (CFD_POISSON_MULTIGRID_ANY, MgaLevel).
+//   the cavity and Rayleigh-Benard at any grid size (CFD_POISSON_MULTIGRID_ANY, MgaLevel),
+//   the channel at any grid size (CFD_POISSON_MULTIGRID_OPEN_ANY, MgoaLevel).
 // A V(nu1, nu2) cycle: red-black Gauss-Seidel sweeps, residual + restriction
 // (the residual never reaches memory), the coarsest level by a fixed number of
 // SOR sweeps in one workgroup, the prolongation added to p. Every constant is
@@ -125,6 +126,26 @@ struct MgaLevel : MgLevel {
   MgaDir x, y;
 };
 
+// The channel at any size: MgoLevel's operator and
+// semi-coarsening with sizes halved rounding up, a direction can be halved
+// while it has at least 8 cells. Each direction is an MgaDir of its own halving
+// count (a for x, b for y): W = 2^a, w = n_0 - (n - 1) W. Here c_lo and c_hi are
+// absolute, cx 2 W / (W + w) and that times W / w (cy in y), and a direction the
+// level's transfer does not halve has no transfer constants (last 0, first
+// n + 1) and is carried over unchanged. Column nx sees the east zero (w + 1) / 2
+// finest spacings away: d = (w + 1) / (2 W), cE = (cx / d) (W / w), g = 1 - 1 / d
+// - MgoLevel's d, cE and g where w = W. Beyond the last coarse x centre the
+// prolongation is linear towards that zero: x.pa[2] = (w + 1) / (w_c + 1) with
+// x.pb[2] = 0, where y (a Neumann end) has 1 and 0. rdiag = 1 / ((cw + ce) + (cs +
+// cn)), index cx | cy << 2 with MgaLevel's classes; every level has n >= 4 in
+// both directions. A cell whose stencil and transfer touch no irregular face
+// takes MgoLevel's expressions, so a grid whose MgoLevel plan stops on a size
+// below 8 gives that plan's bits. tests/mg_open_any_reference.py states every
+// operation.
+struct MgoaLevel : MgoLevel {
+  MgaDir x, y;
+};
+
 template <class Level>
 struct MgPlanOf {
   int levels = 0;
@@ -135,6 +156,7 @@ using MgPlan = MgPlanOf<MgLevel>;
 using MgoPlan = MgPlanOf<MgoLevel>;
 using MgsPlan = MgPlanOf<MgsLevel>;
 using MgaPlan = MgPlanOf<MgaLevel>;
+using MgoaPlan = MgPlanOf<MgoaLevel>;
 
 // The plan of a parameter block, or false with the rule that refused it in
 // `why` (host only: params.cpp).
@@ -142,8 +164,9 @@ bool mg_make_plan(const cfd_params& p, MgPlan& plan, std::string& why);
 bool mgo_make_plan(const cfd_params& p, MgoPlan& plan, std::string& why);
 bool mgs_make_plan(const cfd_params& p, MgsPlan& plan, std::string& why);
 bool mga_make_plan(const cfd_params& p, MgaPlan& plan, std::string& why);
+bool mgoa_make_plan(const cfd_params& p, MgoaPlan& plan, std::string& why);
 
-// Launches (mg.hip), instantiated for the four level types. dlv: the plan's
+// Launches (mg.hip), instantiated for the five level types. dlv: the plan's
 // levels in device memory; L: the host copy of the level that sizes the grid.
 // One colour of a red-black Gauss-Seidel sweep of level l, in place.
 template <class Level>

@@ -215,6 +215,12 @@ namespace {
 
 using namespace cfd;
 
+// omega_c of a level whose larger size is m
+double mg_omega_c(int m) {
+  const double pi = 3.14159265358979323846;
+  return 2.0 / (1.0 + std::sin(pi / (m + 1)));
+}
+
 // What every level holds whatever its operator; returns omega_c.
 double mg_level_base(MgLevelBase& L, int nx, int ny) {
   L.nx = nx;
@@ -223,8 +229,7 @@ double mg_level_base(MgLevelBase& L, int nx, int ny) {
   L.lds_p = L.lds_f = -1;
   const int m = std::max(nx, ny);
   L.coarse_sweeps = 4 * m;
-  const double pi = 3.14159265358979323846;
-  const double omega = 2.0 / (1.0 + std::sin(pi / (m + 1)));
+  const double omega = mg_omega_c(m);
   L.one_m_omega = 1.0 - omega;
   return omega;
 }
@@ -270,6 +275,7 @@ bool mg_finish_plan(MgPlanOf<Level>& plan, int n, const std::string& head, const
 // while its size is even and at least 8 and the block allows it, and a level whose chosen direction(s)
 // cannot be halved is the coarsest. Valid with 2 .. MG_MAX_LEVELS levels. `block` is the step's geometry
 // (MgNoBlock for the channel): it fills its own fields of a level, may forbid a halving, and is halved along.
+// Block::round_up = 1 (the channel at any size) halves odd sizes too, rounding up.
 template <class Level, class Block>
 bool mg_semi_plan(const cfd_params& p, MgPlanOf<Level>& plan, Block block, const std::string& head,
                   const char* second_level_rule, std::string& why) {
@@ -299,7 +305,8 @@ bool mg_semi_plan(const cfd_params& p, MgPlanOf<Level>& plan, Block block, const
     block.fill(L, omega);
     ++n;
     const double q = hy / hx, r = q * q;
-    const bool can_x = nx % 2 == 0 && nx >= 8 && block.can_x(), can_y = ny % 2 == 0 && ny >= 8 && block.can_y(ny);
+    const bool can_x = (Block::round_up || nx % 2 == 0) && nx >= 8 && block.can_x();
+    const bool can_y = (Block::round_up || ny % 2 == 0) && ny >= 8 && block.can_y(ny);
     L.kind = -1;
     if (r > 2.0) {
       if (can_x) L.kind = MGO_X;
@@ -309,13 +316,14 @@ bool mg_semi_plan(const cfd_params& p, MgPlanOf<Level>& plan, Block block, const
       L.kind = MGO_FULL;
     }
     if (L.kind < 0) break;
-    if (L.kind != MGO_Y) nx /= 2, ++a, block.halve_x();
-    if (L.kind != MGO_X) ny /= 2, ++b, block.halve_y();
+    if (L.kind != MGO_Y) nx = (nx + Block::round_up) / 2, ++a, block.halve_x();
+    if (L.kind != MGO_X) ny = (ny + Block::round_up) / 2, ++b, block.halve_y();
   }
   return mg_finish_plan(plan, n, head, second_level_rule, why);
 }
 
 struct MgNoBlock {
+  static constexpr int round_up = 0;
   void fill(MgoLevel&, double) const {}
   bool can_x() const { return true; }
   bool can_y(int) const { return true; }
@@ -328,6 +336,7 @@ struct MgNoBlock {
 // a coarse cell's children are all fluid or all solid and every level keeps the pair A = (jm+1, si+1),
 // B = (jm, si).
 struct MgStepBlock {
+  static constexpr int round_up = 0;
   int si, jm;
   void fill(MgsLevel& L, double omega) const {
     const int nx = L.nx, ny = L.ny;
@@ -585,4 +594,106 @@ extern "C" int cfd_mg_any_level(const cfd_params* p, int level, double* out, int
     for (double v : D->pb) put(v);
   }
   return n == CFD_MG_ANY_LEVEL_DOUBLES ? CFD_OK : CFD_E_STATE;
+}
+
+// The channel's plan at any size: mg_semi_plan halving odd sizes too, then each level's
+// directions and the coefficients that depend on them, as tests/mg_open_any_reference.py (Direction, Level)
+// forms them.
+namespace {
+
+struct MgRoundUpBlock : MgNoBlock {
+  static constexpr int round_up = 1;
+};
+
+// One direction of a level: mga_direction with the direction's own halving count h, the face coefficients
+// times c (cx or cy), no transfer constants where the level's transfer leaves the direction alone, and
+// towards the east zero (x) the weight of the cell beyond the last coarse centre.
+void mgoa_direction(MgaDir& D, int h, int n0, int n, double c, bool halved, bool east) {
+  mga_direction(D, h, n0, n, halved);
+  const double W = std::ldexp(1.0, h), w = (double)(n0 - (long long)(n - 1) * (1LL << h));
+  D.c_lo = c * D.c_lo;
+  D.c_hi = D.c_lo * (W / w);
+  if (!halved) D.single = 0;
+  if (D.last && east) {
+    const double wc = (double)(n0 - (long long)(D.last - 1) * (1LL << (h + 1)));
+    D.pa[2] = (w + 1.0) / (wc + 1.0);
+  }
+}
+
+}  // namespace
+
+bool cfd::mgoa_make_plan(const cfd_params& p, MgoaPlan& plan, std::string& why) {
+  if (p.case_id != CFD_CHANNEL) {
+    why = "any-size open multigrid covers the channel (case rule): the cavity and Rayleigh-Benard have "
+          "CFD_POISSON_MULTIGRID and CFD_POISSON_MULTIGRID_ANY, the step CFD_POISSON_MULTIGRID_STEP";
+    return false;
+  }
+  if (p.nx < 2 || p.ny < 2 || !(p.dx > 0) || !(p.dy > 0)) {
+    why = "any-size open multigrid needs a grid of at least 2 x 2 cells and dx, dy > 0 (grid rule)";
+    return false;
+  }
+  const std::string head = mg_grid_name(p) + " has no any-size open multigrid plan (grid rule): ";
+  if (!mg_semi_plan(p, plan, MgRoundUpBlock{}, head,
+                    "the direction its spacings choose cannot be halved (a size must be at least 8)", why))
+    return false;
+  for (int l = 0; l < plan.levels; ++l) {
+    const MgoaLevel& L = plan.lv[l];
+    if (std::min(L.nx, L.ny) < 4) {
+      why = head + "its level " + std::to_string(l) + ", " + std::to_string(L.nx) + " x " + std::to_string(L.ny) +
+            ", has fewer than 4 cells in a direction";
+      return false;
+    }
+  }
+  for (int l = 0; l < plan.levels; ++l) {
+    MgoaLevel& L = plan.lv[l];
+    mgoa_direction(L.x, L.a, p.nx, L.nx, L.cx, L.kind == MGO_FULL || L.kind == MGO_X, true);
+    mgoa_direction(L.y, L.b, p.ny, L.ny, L.cy, L.kind == MGO_FULL || L.kind == MGO_Y, false);
+    const double W = std::ldexp(1.0, L.a), w = (double)(p.nx - (long long)(L.nx - 1) * (1LL << L.a));
+    const double d = (w + 1.0) / (2.0 * W);  // (w = W: mg_semi_plan's 0.5 + 0.5^(a+1), cE and g)
+    L.cE = (L.cx / d) * (W / w);
+    L.g = 1.0 - 1.0 / d;
+    const double omega = mg_omega_c(std::max(L.nx, L.ny));
+    const double cw[4] = {0.0, L.cx, L.cx, L.x.c_hi}, ce[4] = {L.cx, L.cx, L.x.c_lo, L.cE};
+    const double cs[4] = {0.0, L.cy, L.cy, L.y.c_hi}, cn[4] = {L.cy, L.cy, L.y.c_lo, 0.0};
+    for (int k = 0; k < 16; ++k) {
+      L.rdiag[k] = 1.0 / ((cw[k & 3] + ce[k & 3]) + (cs[k >> 2] + cn[k >> 2]));
+      L.omr[k] = omega * L.rdiag[k];
+    }
+  }
+  return true;
+}
+
+extern "C" int cfd_mg_open_any_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny) {
+  return mg_report_levels<cfd::MgoaPlan>(p, cfd::mgoa_make_plan, levels, level_nx, level_ny);
+}
+
+extern "C" int cfd_mg_open_any_level(const cfd_params* p, int level, double* out, int cap) {
+  if (!p || !out) {
+    cfd::set_last_error("null argument");
+    return CFD_E_ARG;
+  }
+  cfd::MgoaPlan plan;
+  std::string why;
+  if (!cfd::mgoa_make_plan(*p, plan, why)) {
+    cfd::set_last_error(why);
+    return CFD_E_ARG;
+  }
+  if (level < 0 || level >= plan.levels || cap < CFD_MG_OPEN_ANY_LEVEL_DOUBLES) {
+    cfd::set_last_error("cfd_mg_open_any_level: no such level, or fewer than CFD_MG_OPEN_ANY_LEVEL_DOUBLES doubles");
+    return CFD_E_ARG;
+  }
+  const cfd::MgoaLevel& L = plan.lv[level];
+  int n = 0;
+  auto put = [&](double v) { out[n++] = v; };
+  put(L.nx), put(L.ny), put(L.pitch), put(L.lds_p), put(L.lds_f), put(L.coarse_sweeps), put(plan.tail);
+  put(L.kind), put(L.a), put(L.b);
+  put(L.cx), put(L.cy), put(L.cE), put(L.g), put(L.one_m_omega);
+  for (double v : L.rdiag) put(v);
+  for (double v : L.omr) put(v);
+  for (const cfd::MgaDir* D : {&L.x, &L.y}) {
+    put(D->lim), put(D->last), put(D->single), put(D->first), put(D->c_lo), put(D->c_hi), put(D->r0), put(D->r1);
+    for (double v : D->pa) put(v);
+    for (double v : D->pb) put(v);
+  }
+  return n == CFD_MG_OPEN_ANY_LEVEL_DOUBLES ? CFD_OK : CFD_E_STATE;
 }

@@ -1434,12 +1434,12 @@ class Solver {
   }
 
   // ---------------------------------------------------------- multigrid --
-  // The opt-in multigrid solve (mg.hpp): cfd_set_poisson_method. One driver serves the four
-  // schemes (the cavity's, the channel's, the step's, the any-size cavity's): the launches are mg.hip's
+  // The opt-in multigrid solve (mg.hpp): cfd_set_poisson_method. One driver serves the five
+  // schemes (the cavity's, the channel's, the step's, the any-size cavity's and channel's): the launches are mg.hip's
   // templates over the plan's level type, and what a solve does differently by scheme is in the three hooks
   // solve_mg hands to mg_solve.
   int mg_method = CFD_POISSON_SOR;                 // the active method (SOR: none of the state below)
-  std::variant<MgPlan, MgoPlan, MgsPlan, MgaPlan> mg_plan;  // its plan: the alternative mg_method names
+  std::variant<MgPlan, MgoPlan, MgsPlan, MgaPlan, MgoaPlan> mg_plan;  // its plan: the alternative mg_method names
   void* mg_dlv = nullptr;                          // the plan's levels in device memory
   std::vector<double*> mg_p, mg_f;      // levels >= 1: correction and source, rows 0 .. ny+1 of lv.pitch doubles
   // Fused smoothing (mg_smooth_tile_kernel) writes to a second buffer: mg_q[l] for the multi-launch levels
@@ -1483,7 +1483,7 @@ class Solver {
       return;
     }
     if (method != CFD_POISSON_MULTIGRID && method != CFD_POISSON_MULTIGRID_OPEN && method != CFD_POISSON_MULTIGRID_STEP &&
-        method != CFD_POISSON_MULTIGRID_ANY)
+        method != CFD_POISSON_MULTIGRID_ANY && method != CFD_POISSON_MULTIGRID_OPEN_ANY)
       throw Error(CFD_E_ARG, "unknown cfd_poisson_method");
     if (S.size() != 1) throw Error(CFD_E_ARG, "multigrid runs on one strip (strip rule): this solver has n_strips > 1");
     if (comm) throw Error(CFD_E_ARG, "multigrid runs without ranks (rank rule): this is a rank solver");
@@ -1494,6 +1494,7 @@ class Solver {
     if (method == CFD_POISSON_MULTIGRID_STEP) mg_install<MgsPlan>(method, mgs_make_plan);
     else if (method == CFD_POISSON_MULTIGRID_OPEN) mg_install<MgoPlan>(method, mgo_make_plan);
     else if (method == CFD_POISSON_MULTIGRID_ANY) mg_install<MgaPlan>(method, mga_make_plan);
+    else if (method == CFD_POISSON_MULTIGRID_OPEN_ANY) mg_install<MgoaPlan>(method, mgoa_make_plan);
     else mg_install<MgPlan>(method, mg_make_plan);
     mg_nu1 = nu1;
     mg_nu2 = nu2;
@@ -1692,25 +1693,30 @@ class Solver {
       };
       if (mg_method == CFD_POISSON_MULTIGRID) cavity(std::get<MgPlan>(mg_plan));
       else cavity(std::get<MgaPlan>(mg_plan));
-    } else if (mg_method == CFD_POISSON_MULTIGRID_OPEN) {
+    } else if (mg_method == CFD_POISSON_MULTIGRID_OPEN || mg_method == CFD_POISSON_MULTIGRID_OPEN_ANY) {
       // channel-01.cpp:642-688 with a V-cycle for the sweep: a warm start from the field the solver holds; after
       // a cycle the reference's ghost refresh (531-541: west and east columns, then south and north rows) and its
       // own residual on those ghosts. Copied back: rows 1 .. ny whole (their ghost columns are refreshed), the
       // ghost rows over columns 1 .. nx - the corners stay p's own.
-      mg_solve(
-          std::get<MgoPlan>(mg_plan), out, warm,
-          [&](double* buf, long long& launches) {
-            res_refresh(s.g, buf, st);
-            check_launch("mg_refresh");
-            launches += 2;
-            return mg_open_residual<CHANNEL>(buf);
-          },
-          [&](double* p0, const double* q) {
-            HIPC(hipMemcpyAsync(p0 + pitch, q + pitch, (size_t)P.ny * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
-            HIPC(hipMemcpyAsync(p0 + 1, q + 1, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-            const size_t top = (size_t)(P.ny + 1) * pitch + 1;
-            HIPC(hipMemcpyAsync(p0 + top, q + top, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-          });
+      // The any-size method's level 0 is the same operator: the same three hooks around its own plan.
+      auto channel = [&](const auto& plan) {
+        mg_solve(
+            plan, out, warm,
+            [&](double* buf, long long& launches) {
+              res_refresh(s.g, buf, st);
+              check_launch("mg_refresh");
+              launches += 2;
+              return mg_open_residual<CHANNEL>(buf);
+            },
+            [&](double* p0, const double* q) {
+              HIPC(hipMemcpyAsync(p0 + pitch, q + pitch, (size_t)P.ny * pitch * sizeof(double), hipMemcpyDeviceToDevice, st));
+              HIPC(hipMemcpyAsync(p0 + 1, q + 1, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+              const size_t top = (size_t)(P.ny + 1) * pitch + 1;
+              HIPC(hipMemcpyAsync(p0 + top, q + top, (size_t)P.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+            });
+      };
+      if (mg_method == CFD_POISSON_MULTIGRID_OPEN) channel(std::get<MgoPlan>(mg_plan));
+      else channel(std::get<MgoaPlan>(mg_plan));
     } else {
       // backwards_step-01.cpp:872-939 with a V-cycle for the sweep: a warm start; after a cycle the reference's
       // ghost and solid refresh (685-740) and its own residual over the fluid cells. Copied back: everything

@@ -35,6 +35,7 @@ struct Options {
   bool multigrid_open = false;
   bool multigrid_step = false;
   bool multigrid_any = false;
+  bool multigrid_open_any = false;
   int mg_cycles = 0;
   std::string outdir = "vtk_output";
 };
@@ -44,7 +45,8 @@ inline void usage(const char* prog) {
             << " [--Re R | --Ra RA --Pr PR] [--Nx N] [--Ny N] [--dt DT] [--final-time T] [--steps K] [--max-iters N]\n"
                "       [--save-interval N] [--print-interval N] [--output-dir DIR] [--no-vtk]\n"
                "       [--device D] [--strips S] [--check-every C] [--red-black] [--exact]\n"
-               "       [--multigrid | --multigrid-open | --multigrid-step | --multigrid-any [--mg-cycles N]]\n"
+               "       [--multigrid | --multigrid-open | --multigrid-step | --multigrid-any | --multigrid-open-any\n"
+               "        [--mg-cycles N]]\n"
                "  default: the reference's lexicographic SOR order (bit-identical output; strips allowed)\n"
                "  --red-black: red-black SOR order (the multi-GPU order; the same answer where the\n"
                "               solve converges, a different iterate where it hits the sweep cap)\n"
@@ -59,6 +61,9 @@ inline void usage(const char* prog) {
                "  --multigrid-any: the cavity's and Rayleigh-Benard's multigrid solve at any grid whose smaller side is\n"
                "               at least 8 (sizes halved rounding up; one strip); cycles in the iteration column; not with\n"
                "               the other three flags\n"
+               "  --multigrid-open-any: the channel's multigrid solve at any grid size (--multigrid-open with sizes\n"
+               "               halved rounding up while they are at least 8; one strip); cycles in the iteration column;\n"
+               "               not with the other four flags\n"
                "  --mg-cycles N: at most N cycles per solve (default 50)\n";
 }
 
@@ -92,6 +97,7 @@ inline Options parse(int argc, char** argv) {
     else if (a == "--multigrid-open") o.multigrid_open = true;
     else if (a == "--multigrid-step") o.multigrid_step = true;
     else if (a == "--multigrid-any") o.multigrid_any = true;
+    else if (a == "--multigrid-open-any") o.multigrid_open_any = true;
     else if (a == "--mg-cycles") o.mg_cycles = std::atoi(next());
     else if (a == "--device") o.device = std::atoi(next());
     else if (a == "--strips") o.strips = std::atoi(next());
@@ -112,6 +118,11 @@ inline Options parse(int argc, char** argv) {
   }
   if (o.multigrid_any && (o.multigrid || o.multigrid_open || o.multigrid_step)) {
     std::cerr << "--multigrid-any excludes --multigrid, --multigrid-open and --multigrid-step\n";
+    usage(argv[0]);
+    std::exit(2);
+  }
+  if (o.multigrid_open_any && (o.multigrid || o.multigrid_open || o.multigrid_step || o.multigrid_any)) {
+    std::cerr << "--multigrid-open-any excludes --multigrid, --multigrid-open, --multigrid-step and --multigrid-any\n";
     usage(argv[0]);
     std::exit(2);
   }
@@ -202,17 +213,19 @@ inline int run_case(int case_id, int argc, char** argv) {
   cfd_solver* s = cfd_create(&p, o.device, o.strips);
   if (!s) die("cfd_create");
   int iter_cap = p.max_iters;  // the solve's cap: SOR iterations, or multigrid cycles
-  if (o.multigrid || o.multigrid_open || o.multigrid_step || o.multigrid_any) {
+  if (o.multigrid || o.multigrid_open || o.multigrid_step || o.multigrid_any || o.multigrid_open_any) {
     cfd_mg_options mo = {0, 0, o.mg_cycles > 0 ? o.mg_cycles : 0};
-    const int method = o.multigrid_any    ? CFD_POISSON_MULTIGRID_ANY
-                       : o.multigrid_step ? CFD_POISSON_MULTIGRID_STEP
-                       : o.multigrid      ? CFD_POISSON_MULTIGRID
-                                          : CFD_POISSON_MULTIGRID_OPEN;
+    const int method = o.multigrid_open_any ? CFD_POISSON_MULTIGRID_OPEN_ANY
+                       : o.multigrid_any    ? CFD_POISSON_MULTIGRID_ANY
+                       : o.multigrid_step   ? CFD_POISSON_MULTIGRID_STEP
+                       : o.multigrid        ? CFD_POISSON_MULTIGRID
+                                            : CFD_POISSON_MULTIGRID_OPEN;
     if (cfd_set_poisson_method(s, method, &mo) != CFD_OK)
-      die(o.multigrid_any    ? "--multigrid-any"
-          : o.multigrid_step ? "--multigrid-step"
-          : o.multigrid      ? "--multigrid"
-                             : "--multigrid-open");
+      die(o.multigrid_open_any ? "--multigrid-open-any"
+          : o.multigrid_any    ? "--multigrid-any"
+          : o.multigrid_step   ? "--multigrid-step"
+          : o.multigrid        ? "--multigrid"
+                               : "--multigrid-open");
     iter_cap = o.mg_cycles > 0 ? o.mg_cycles : 50;
   }
   std::vector<std::string> files;

@@ -183,7 +183,8 @@ enum cfd_poisson_method {
   CFD_POISSON_MULTIGRID = 1,      /* the cavity and Rayleigh-Benard */
   CFD_POISSON_MULTIGRID_OPEN = 2, /* the channel (below; added within ABI 14) */
   CFD_POISSON_MULTIGRID_STEP = 3, /* the backwards-facing step (below; added within ABI 14) */
-  CFD_POISSON_MULTIGRID_ANY = 4   /* the cavity and Rayleigh-Benard at any grid size (below; added within ABI 14) */
+  CFD_POISSON_MULTIGRID_ANY = 4,  /* the cavity and Rayleigh-Benard at any grid size (below; added within ABI 14) */
+  CFD_POISSON_MULTIGRID_OPEN_ANY = 5 /* the channel at any grid size (below; added within ABI 14) */
 };
 typedef struct cfd_mg_options {
   int pre_sweeps, post_sweeps, max_cycles;  /* 0 (or a NULL options pointer): 2, 2, 50 */
@@ -274,6 +275,39 @@ int cfd_mg_step_plan(const cfd_params* p, int* levels, int* level_nx, int* level
 #define CFD_MG_ANY_LEVEL_DOUBLES 72
 int cfd_mg_any_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny);
 int cfd_mg_any_level(const cfd_params* p, int level, double* out, int cap);
+/*
+ * CFD_POISSON_MULTIGRID_OPEN_ANY: the channel's multigrid solve at any grid size, a
+ * fifth method beside the other four - same options, same cfd_get_mg_info, cfd_timing.sor_kernel
+ * reports CFD_SOR_MULTIGRID, CFD_POISSON_SOR switches back. New symbols and one enum value within
+ * ABI 14. CFD_POISSON_MULTIGRID_OPEN, its bits and its refusals are unchanged.
+ *
+ * The solve is CFD_POISSON_MULTIGRID_OPEN's (warm start, the reference's ghost refresh, residual and
+ * tolerance, the same semi-coarsening rule) on levels halved rounding up: a direction can be halved
+ * while its size is >= 8, n_{l+1} = ceil(n_l / 2). A direction halved h times has cells of 2^h
+ * finest cells and a last one of what is left up to the wall (1 .. 2^h), so the walls and the east
+ * zero stay where the finest grid has them; a direction a transfer does not halve is carried over.
+ * The operator is the finite-volume one on that grid; column nx sees the zero (w + 1) / 2 finest
+ * spacings from its centre. The restriction is the volume-weighted mean over a coarse cell's
+ * children (one child where a halved size is odd), the prolongation linear between coarse centres,
+ * constant beyond a Neumann end and linear towards the zero beyond the last coarse x centre. Where
+ * CFD_POISSON_MULTIGRID_OPEN's plan stops on a size below 8 (96 x 32, 256 x 32, 512 x 64,
+ * 4096 x 512) the plan, the cycle count, the residual and p are that method's, bit for bit. Valid
+ * with 2 .. 16 levels, a coarsest level of at most 4096 cells and at least 4 cells per direction
+ * on every level: the reference's 93 x 31, 126 x 90, 1000 x 100, 4000 x 500 all have plans.
+ * Refusals (CFD_E_ARG, cfd_last_error naming the rule): the cavity, Rayleigh-Benard and the step
+ * (case rule: they have methods 1, 4 and 3), a grid without a valid plan such as 13 x 5 (grid rule),
+ * more than one strip (strip rule), rank solvers (rank rule), bad options.
+ *
+ * cfd_mg_open_any_plan (host only): as cfd_mg_open_plan. cfd_mg_open_any_level (host only) writes
+ * every constant of one level of the plan as doubles, for comparison with
+ * tests/mg_open_any_reference.py: nx, ny, pitch, lds_p, lds_f, coarse_sweeps, the plan's tail;
+ * kind, a, b; cx, cy, cE, g, 1 - omega_c; rdiag[16]; omr[16]; then per direction (x, y) lim, last,
+ * single, first, c_lo, c_hi, r0, r1, pa[3], pb[3]. CFD_MG_OPEN_ANY_LEVEL_DOUBLES doubles in all;
+ * `cap` is the room in `out`.
+ */
+#define CFD_MG_OPEN_ANY_LEVEL_DOUBLES 75
+int cfd_mg_open_any_plan(const cfd_params* p, int* levels, int* level_nx, int* level_ny);
+int cfd_mg_open_any_level(const cfd_params* p, int level, double* out, int cap);
 
 /* Library / ABI info. */
 int cfd_abi_version(void);

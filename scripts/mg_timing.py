@@ -23,7 +23,10 @@ JSON file per grid under --out.
   python scripts/mg_timing.py --case step --sizes 256x32 1024x128 8192x512 --out profiles/mg --commit <hash>
   python scripts/mg_timing.py --method multigrid-any --sizes 1000x1000 4095x4095 --out profiles/mg --commit <hash>
 
---method multigrid-any (the cavity at any grid size) writes mg_timing_cavity_any_<size>.json.
+  python scripts/mg_timing.py --case channel --method multigrid-open-any --sizes 4000x500 4095x511 4096x512 --out profiles/mg --commit <hash>
+
+--method multigrid-any (the cavity at any grid size) writes mg_timing_cavity_any_<size>.json,
+--method multigrid-open-any (the channel at any grid size) mg_timing_channel_open_any_<size>.json.
 
 The channel's and the step's run fails (exit 1) if a multigrid solve ends above its tolerance.
 """
@@ -96,9 +99,10 @@ def run(cp, steps, warmup, **kw):
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--case", choices=["cavity", "channel", "step"], default="cavity")
-    ap.add_argument("--method", choices=["multigrid", "multigrid-open", "multigrid-step", "multigrid-any"], default=None,
+    ap.add_argument("--method", choices=["multigrid", "multigrid-open", "multigrid-step", "multigrid-any", "multigrid-open-any"],
+                    default=None,
                     help="default: multigrid for the cavity, multigrid-open for the channel, multigrid-step for the step;\n"
-                         "multigrid-any: the cavity at any grid size")
+                         "multigrid-any: the cavity at any grid size; multigrid-open-any: the channel at any grid size")
     ap.add_argument("--re", type=float, default=None, help="default: 1000; the step: 400")
     ap.add_argument("--sizes", nargs="+", default=None, help="default: 1024x1024 4096x4096 992x992 (cavity), "
                     "4096x512 1024x128 (channel), 256x32 1024x128 8192x512 (step)")
@@ -132,7 +136,7 @@ def main() -> int:
         if a.case != "cavity" and not (all(v22["converged"]) and all(c22["converged"])):
             ok = False
             print(f"{nx}x{ny}: a multigrid solve ended above its tolerance", file=sys.stderr)
-        tag = a.case + ("_any" if method == "multigrid-any" else "")
+        tag = a.case + {"multigrid-any": "_any", "multigrid-open-any": "_open_any"}.get(method, "")
         path = os.path.join(a.out, f"mg_timing_{tag}_{nx}x{ny}.json")
         with open(path, "w") as fh:
             json.dump(rec, fh, indent=1)
