@@ -216,30 +216,56 @@ double orc_source(orc_state* s) {
     return max_source;
   }
   /* channel-01.cpp:608-629, backwards_step-01.cpp:825-866 */
+  max_source = orc_source_raw(s);
+  if (max_source > 0) {
+    const int step = s->P.case_id == ORC_BACKSTEP;
+    const unsigned char* fl = s->fluid;
+    double mean = 0.0;
+    for (int j = 1; j <= ny; ++j)
+      for (int i = 1; i <= nx; ++i)
+        if (!step || AT(fl, j, i)) mean += AT(f, j, i);
+    orc_subtract_mean(s, mean);
+  }
+  return max_source;
+}
+
+double orc_source_raw(orc_state* s) {
+  /* the open cases' f before the mean removal: channel-01.cpp:608-619,
+   * backwards_step-01.cpp:825-841; returns max|f| */
+  const int W = s->W, nx = s->P.nx, ny = s->P.ny;
+  const double* us = s->f[ORC_F_US];
+  const double* vs = s->f[ORC_F_VS];
+  double* f = s->f[ORC_F_SRC];
   const int step = s->P.case_id == ORC_BACKSTEP;
   const unsigned char* fl = s->fluid;
   const double idx = 1.0 / s->P.dx, idy = 1.0 / s->P.dy;
   const double coeff = s->P.rho / s->P.dt;
+  double max_source = 0.0;
   for (int j = 1; j <= ny; ++j)
     for (int i = 1; i <= nx; ++i) {
       if (step && !AT(fl, j, i)) { AT(f, j, i) = 0.0; continue; }
       AT(f, j, i) = coeff * ((AT(us, j, i) - AT(us, j, i - 1)) * idx + (AT(vs, j, i) - AT(vs, j - 1, i)) * idy);
       max_source = fmax(max_source, fabs(AT(f, j, i)));
     }
-  if (max_source > 0) {
-    double mean = 0.0;
-    int cnt = 0;
-    for (int j = 1; j <= ny; ++j)
-      for (int i = 1; i <= nx; ++i)
-        if (!step || AT(fl, j, i)) { mean += AT(f, j, i); ++cnt; }
-    if (cnt > 0) {
-      mean /= (double)cnt;
-      for (int j = 1; j <= ny; ++j)
-        for (int i = 1; i <= nx; ++i)
-          if (!step || AT(fl, j, i)) AT(f, j, i) -= mean;
-    }
-  }
   return max_source;
+}
+
+void orc_subtract_mean(orc_state* s, double total) {
+  /* channel-01.cpp:621-628, backwards_step-01.cpp:844-865, with the sum of f
+   * over the fluid cells given (orc_source: the reference's sequential sum) */
+  const int W = s->W, nx = s->P.nx, ny = s->P.ny;
+  const int step = s->P.case_id == ORC_BACKSTEP;
+  const unsigned char* fl = s->fluid;
+  double* f = s->f[ORC_F_SRC];
+  int cnt = 0;
+  for (int j = 1; j <= ny; ++j)
+    for (int i = 1; i <= nx; ++i)
+      if (!step || AT(fl, j, i)) ++cnt;
+  if (cnt == 0) return;
+  const double mean = total / (double)cnt;
+  for (int j = 1; j <= ny; ++j)
+    for (int i = 1; i <= nx; ++i)
+      if (!step || AT(fl, j, i)) AT(f, j, i) -= mean;
 }
 
 /* ----------------------------------------------------------- Poisson --- */

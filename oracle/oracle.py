@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liboracle.so")
 
 LEX, RB = 0, 1
+CAVITY, CHANNEL, BACKSTEP, RAYLEIGH_BENARD = range(4)  # enum ORC_CAVITY .. ORC_RBC
 F_P, F_SRC, F_RES, F_US, F_VS, F_U, F_V, F_UC, F_VC, F_T, F_T2 = range(11)
 FIELD_IDS = {"p": F_P, "src": F_SRC, "res": F_RES, "us": F_US, "vs": F_VS, "u": F_U, "v": F_V, "uc": F_UC,
              "vc": F_VC, "t": F_T}
@@ -59,6 +60,9 @@ def lib() -> ctypes.CDLL:
         L.orc_velocity_bc.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.orc_source.restype = ctypes.c_double
         L.orc_source.argtypes = [ctypes.c_void_p]
+        L.orc_source_raw.restype = ctypes.c_double
+        L.orc_source_raw.argtypes = [ctypes.c_void_p]
+        L.orc_subtract_mean.argtypes = [ctypes.c_void_p, ctypes.c_double]
         ip, dp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
         L.orc_poisson.argtypes = [ctypes.c_void_p, ctypes.c_int, ip, dp]
         L.orc_poisson_every.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ip, dp]
@@ -119,8 +123,23 @@ class Oracle:
     def tentative(self) -> None:
         lib().orc_tentative(self.h)
 
-    def source(self) -> float:
-        return lib().orc_source(self.h)
+    def source(self, total=None) -> float:
+        """total: None (the reference's sequential sum of the open cases' mean
+        removal) or a callable raw_f -> total that restates another summation
+        order (tests/rb_sums.py: the GPU's red-black tree sum). The cavity and
+        Rayleigh-Benard remove no mean: total is not called."""
+        if total is None or self.cp.case_id in (CAVITY, RAYLEIGH_BENARD):
+            return lib().orc_source(self.h)
+        m = lib().orc_source_raw(self.h)
+        if m > 0:
+            lib().orc_subtract_mean(self.h, float(total(self.field("src"))))
+        return m
+
+    def kinetic_energy(self, ke_total) -> float:
+        """The average kinetic energy of orc_stats with its sum restated: ke_total is a
+        callable (uc, vc) -> the sum of 0.5 * (uc*uc + vc*vc) over the fluid cells. Run
+        after centers() (or stats())."""
+        return float(ke_total(self.field("uc"), self.field("vc"))) / float(self.fluid_count())
 
     def poisson(self, ordering: int | None = None, check_every: int = 1) -> tuple[int, float]:
         """check_every > 1: the stop rule on multiples of check_every only (orc_poisson_every)."""
@@ -164,23 +183,25 @@ class Oracle:
     def nusselt(self) -> float:
         return lib().orc_nusselt(self.h)
 
-    def step(self, check_every: int = 1) -> tuple[int, float]:
-        if check_every > 1:
-            return self.step_phases(check_every)
+    def step(self, check_every: int = 1, source_total=None) -> tuple[int, float]:
+        """source_total: as source(total=...), for the step's mean removal."""
+        if check_every > 1 or source_total is not None:
+            return self.step_phases(check_every, source_total)
         it, res = ctypes.c_int(), ctypes.c_double()
         lib().orc_step(self.h, self.ordering, ctypes.byref(it), ctypes.byref(res))
         return it.value, res.value
 
-    def step_phases(self, check_every: int) -> tuple[int, float]:
+    def step_phases(self, check_every: int = 1, source_total=None) -> tuple[int, float]:
         """orc_step composed from the phases, in its order for the case, with
-        the solve's stop rule tested every check_every iterations."""
+        the solve's stop rule tested every check_every iterations and the open
+        cases' mean removal given source_total (source(total=...))."""
         case = self.cp.case_id
-        if case in (0, 3):  # cavity, Rayleigh-Benard
+        if case in (CAVITY, RAYLEIGH_BENARD):
             self.velocity_bc(False)
-            if case == 3:
+            if case == RAYLEIGH_BENARD:
                 self.temperature_bc()
             self.tentative()
-            if case == 3:
+            if case == RAYLEIGH_BENARD:
                 self.thermal()
             self.source()
             r = self.poisson_every(check_every)
@@ -188,7 +209,7 @@ class Oracle:
             return r
         self.tentative()
         self.velocity_bc(True)
-        self.source()
+        self.source(source_total)
         r = self.poisson_every(check_every)
         self.correct()
         self.velocity_bc(False)

@@ -11,7 +11,8 @@ against the CPU oracle.
   meets the reference's stop rule.
 * configs[3] backwards step Re=400, 8192x512 on 4 ranks (loopback transport,
   the RCCL code path): every rank's rows against the red-black oracle, not
-  only against one GPU domain.
+  only against one GPU domain, bit for bit (the source mean's per-rank tree
+  sums and their rank-order all-reduce restated, tests/rb_sums.py).
 * configs[4] Rayleigh-Benard Ra=1e6 Pr=0.71, 8192x2048 (parity unpinned: no
   reference solver): a whole step bit-exact against the oracle's restatement,
   and 4 strips == one domain, at the full size.
@@ -27,7 +28,7 @@ import cfd_amd as C  # noqa: E402
 import oracle as O  # noqa: E402
 from test_gpu_fullsize import cavity_residual  # noqa: E402
 from test_gpu_parity import assert_bits, centerlines, ofield, rel_l2  # noqa: E402
-from test_gpu_ranks import run_ranks  # noqa: E402
+from test_gpu_ranks import assert_rank_equals, oracle_run, run_ranks  # noqa: E402
 
 
 def test_config0_cavity_re100_128_bitexact_and_reference_order():
@@ -92,19 +93,9 @@ def test_config3_backstep_8192x512_four_ranks_vs_oracle():
     cp = C.make_params("backwards_step", re=400.0, nx=8192, ny=512, max_iters=40)
     steps = 2
     res = run_ranks(cp, 4, steps)
-    o = O.Oracle(cp, ordering=O.RB)
-    o.velocity_bc(False)
-    its = [o.step() for _ in range(steps)]
+    ref = oracle_run(cp, steps, 4, ranks=True)  # source mean: per-rank tree sums, all-reduced in rank order
     for r in res:
-        assert [i for i, _ in r["its"]] == [i for i, _ in its]
-        j0, j1 = r["rows"]
-        first = 0 if j0 == 1 else j0
-        for name in ("u", "v", "p"):
-            ref = ofield(o, name, cp)
-            last = min(j1 + 1 if j1 == cp.ny else j1, ref.shape[0] - 1)
-            # source mean: per-rank tree sums all-reduced vs one sequential sum
-            np.testing.assert_allclose(r[name], ref[first:last + 1], rtol=0,
-                                       atol=1e-10 * max(np.abs(ref).max(), 1.0), err_msg=f"{name} rows {j0}-{j1}")
+        assert_rank_equals(r, ref, cp)
 
 
 def test_config4_rayleigh_benard_8192x2048_step_vs_oracle():

@@ -8,7 +8,10 @@
   reference's scheme drains flux along the channel; the CPU
   oracle run of this same case gives flux 0.95287 at x=0.8L, as the GPU does.
 * configs[3] backwards step 8192x512 over 4 ranks: 4 rank solvers (loopback
-  transport, host threads) against one domain.
+  transport, host threads) against the red-black oracle with the ranks' source
+  sums restated (tests/rb_sums.py), and one GPU domain against the oracle with
+  its own strip's sum restated (the two tree sums differ in the last bits), each
+  bit for bit; the iteration counts of the two equal.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import cfd_amd as C  # noqa: E402
-from test_gpu_ranks import run_ranks, single  # noqa: E402
+from test_gpu_ranks import assert_rank_equals, assert_single_equals, oracle_run, run_ranks, single  # noqa: E402
 
 
 def test_channel_poiseuille_profile():
@@ -63,10 +66,8 @@ def test_backstep_8192x512_four_ranks():
     cp = C.make_params("backwards_step", re=400.0, nx=8192, ny=512, max_iters=300)
     res = run_ranks(cp, 4, 2)
     s, its = single(cp, 2)
-    ref = s.field("u")
+    assert_single_equals(s, its, oracle_run(cp, 2))
+    ref = oracle_run(cp, 2, 4, ranks=True)
     for r in res:
         assert [i for i, _ in r["its"]] == [i for i, _ in its]
-        j0, j1 = r["rows"]
-        first = 0 if j0 == 1 else j0
-        last = j1 + 1 if j1 == cp.ny else j1
-        np.testing.assert_allclose(r["u"], ref[first:last + 1], rtol=0, atol=1e-9 * np.abs(ref).max())
+        assert_rank_equals(r, ref, cp)

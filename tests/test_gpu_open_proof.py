@@ -8,7 +8,9 @@ convergence test with the open cases' K = 2 (idx2 + idy2)(1 - w)/w.
 The launch must be invisible: the same iteration counts, residuals and
 fields, bit for bit, as exact residuals in every sweep (pair launches) and as
 the red-black oracle; converging solves end with an iteration the proof
-leaves open (exact fallback)."""
+leaves open (exact fallback). Strips whose rows begin on the single domain's
+block rows sum the source mean in the same order (tests/rb_sums.py): they equal
+one domain bit for bit."""
 from __future__ import annotations
 
 import numpy as np
@@ -18,8 +20,9 @@ pytestmark = pytest.mark.gpu
 
 import cfd_amd as C  # noqa: E402
 import oracle as O  # noqa: E402
+import rb_sums as R  # noqa: E402
 from cfd_amd import _lib  # noqa: E402
-from test_gpu_parity import assert_bits  # noqa: E402
+from test_gpu_parity import assert_bits, ofield  # noqa: E402
 
 SOLVERS = {"channel": C.ChannelSolver, "backwards_step": C.BackwardsStepSolver}
 FIELDS = ("p", "u", "v")
@@ -82,18 +85,46 @@ def test_open_proof_vs_red_black_oracle(case, nx, ny, cap):
     g.close()
 
 
+_ORACLE = {}
+
+
+def oracle_two_steps(case, nx):
+    """Two steps of the red-black oracle at nx x 240, cap 600, the source mean's tree sum
+    restated for one strip (the same total on 2 and 3 strips); once per grid."""
+    if (case, nx) not in _ORACLE:
+        cp = C.make_params(case, nx=nx, ny=240, max_iters=600)
+        o = O.Oracle(cp, ordering=O.RB)
+        o.velocity_bc(False)
+        hook = R.source_hook(o, R.strips_of(cp.ny, 1))
+        hist = [o.step(source_total=hook) for _ in range(2)]
+        _ORACLE[(case, nx)] = (hist, {n: ofield(o, n, cp).copy() for n in FIELDS})
+    return _ORACLE[(case, nx)]
+
+
 @pytest.mark.parametrize("case,nx", [("channel", 400), ("backwards_step", 400), ("backwards_step", 1600)])
 @pytest.mark.parametrize("strips", [2, 3])
 def test_open_proof_on_strips(case, nx, strips):
     """Strips on one device (8-row halos exchanged once per launch: the
     4-sweep pipeline's depth is 8). Step 1600 wide: the left-of-column tile
-    class on strips below, across and above the block's lower edge."""
+    class on strips below, across and above the block's lower edge.
+    240 rows on 2 or 3 strips: every strip begins on a block row of the single
+    domain (4 rows), so the source mean's partial sums are the same blocks in the
+    same order (tests/rb_sums.py) and the two runs equal bit for bit; and both
+    equal the red-black oracle with that total restated."""
     cp = C.make_params(case, nx=nx, ny=240, max_iters=600)
+    layout = R.strips_of(cp.ny, strips)
+    assert all((j0 - 1) % 4 == 0 for j0, _ in layout)
+    probe = np.random.default_rng(strips).standard_normal((cp.ny + 2, cp.nx + 2))
+    assert np.array_equal(R.partials(probe, layout).view(np.int64), R.partials(probe, R.strips_of(cp.ny, 1)).view(np.int64))
     h1, f1, _ = run(case, cp, 2)
     h2, f2, t2 = run(case, cp, 2, strips=strips)
     assert h1 == h2
     for n in FIELDS:
-        np.testing.assert_allclose(f2[n], f1[n], rtol=0, atol=1e-12 * max(1.0, np.abs(f1[n]).max()))
+        assert_bits(f2[n], f1[n], f"{case} {nx}x240 on {strips} strips, {n}")
+    ho, fo = oracle_two_steps(case, nx)
+    assert h2 == ho
+    for n in FIELDS:
+        assert_bits(f2[n], fo[n], f"{case} {nx}x240 on {strips} strips, {n} vs red-black oracle")
 
 
 def test_open_proof_full_size_channel_capped():

@@ -3,7 +3,16 @@ one process and exchange halos / all-reduce through the library's in-process
 loopback transport (RCCL refuses two ranks on one device). Everything but the
 RCCL calls themselves is the code the 8-GPU run executes: rank strips, halo
 row indices, the residual all-reduce feeding each rank's convergence test,
-the source-sum and stats reductions, rank-local field transfer."""
+the source-sum and stats reductions, rank-local field transfer.
+
+The open cases' source mean and every case's kinetic energy are tree sums whose
+order depends on the layout (each rank sums its own strip, the loopback
+all-reduce adds the ranks 0, 1, 2, ..): a rank run and a single-domain run
+differ in the last bits, so each is held to the red-black oracle with its own
+layout's total restated (tests/rb_sums.py): (iterations, residual) of every
+step, u, v, p on the owned rows, max divergence and kinetic energy, bit for
+bit. The claim for three or more ranks is the loopback transport's: a real
+RCCL all-reduce over more than two devices states no order."""
 from __future__ import annotations
 
 import threading
@@ -15,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 import cfd_amd as C  # noqa: E402
 import oracle as O  # noqa: E402
+import rb_sums as R  # noqa: E402
 from cfd_amd import _lib  # noqa: E402
 from cfd_amd.dist import strip_rows  # noqa: E402
 
@@ -35,7 +45,7 @@ def run_ranks(cp, world, steps, check_every=1, timing=False, **kw):
                 s.applyBoundaryConditions()
             its = [s.step() for _ in range(steps)]
             md, ke = s.statistics()
-            results[r] = dict(rows=s.owned_rows(), u=s.field("u"), v=s.field("v"), p=s.field("p"), its=its,
+            results[r] = dict(rows=s.owned_rows(), u=s.field("u"), v=s.field("v"), p=s.field("p"), src=s.field("src"), its=its,
                               stats=(md, ke), overlapped=s.timing().poisson_overlapped,
                               fallbacks=s.timing().proof_fallbacks, launches=s.timing().poisson_launches,
                               sweeps=s.timing().poisson_sweeps, plan=s.sor_plan())
@@ -54,6 +64,47 @@ def run_ranks(cp, world, steps, check_every=1, timing=False, **kw):
     return results
 
 
+FIELDS = ("u", "v", "p", "src")
+
+
+def oracle_run(cp, steps, n=1, ranks=False):
+    """The red-black oracle's run with the tree sums restated for n strips or n ranks:
+    its, fields, (max divergence, kinetic energy)."""
+    o = O.Oracle(cp, ordering=O.RB)
+    o.velocity_bc(False)  # (the open cases' constructor; the cavity's applyBoundaryConditions)
+    layout = R.layout(cp.ny, n, ranks)
+    hook = None if cp.case_id == C.CAVITY else R.source_hook(o, layout, ranks)
+    its = [o.step(source_total=hook) for _ in range(steps)]
+    md, _ = o.stats()
+    out = dict(its=its, stats=(md, R.oracle_ke(o, layout, ranks)))
+    for n_ in FIELDS:
+        a = o.field(n_)
+        out[n_] = (a[:, :cp.nx + 1] if n_ == "u" else a[:cp.ny + 1] if n_ == "v" else a).copy()
+    return out
+
+
+def assert_rank_equals(r, ref, cp, stats=True):
+    """A rank's result against a whole-domain run (the oracle's): bits on its rows."""
+    assert r["its"] == ref["its"], r["rows"]
+    j0, j1 = r["rows"]
+    first = 0 if j0 == 1 else j0
+    for n in FIELDS:
+        last = min(j1 + 1 if j1 == cp.ny else j1, ref[n].shape[0] - 1)
+        a, b = r[n], ref[n][first:last + 1]
+        assert a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64)), (n, r["rows"])
+    if stats:
+        assert r["stats"] == ref["stats"], r["rows"]
+
+
+def assert_single_equals(s, its, ref):
+    """A single-domain solver against the oracle's run with one strip's restated sums."""
+    assert its == ref["its"]
+    for n in FIELDS:
+        a = s.field(n)
+        assert np.array_equal(a.view(np.int64), ref[n].view(np.int64)), n
+    assert s.statistics() == ref["stats"]
+
+
 def single(cp, steps, **kw):
     s = C.solver_for(cp, ordering="rb", **kw)
     if cp.case_id == C.CAVITY:
@@ -68,29 +119,15 @@ def test_rank_path_equals_single_domain(case, world, steps):
     cp = C.reference_defaults(case)
     res = run_ranks(cp, world, steps)
     s, its = single(cp, steps)
-    ref = {n: s.field(n) for n in ("u", "v", "p")}
+    ref = {n: s.field(n) for n in FIELDS}
+    if case == "cavity":  # no sum feeds the state: the ranks equal one domain
+        ref["its"] = its
+        for r in res:
+            assert_rank_equals(r, ref, cp, stats=False)
+    oref = oracle_run(cp, steps, world, ranks=True)
     for r in res:
-        if case == "cavity":
-            assert r["its"] == its
-        else:
-            assert [i for i, _ in r["its"]] == [i for i, _ in its]
-        j0, j1 = r["rows"]
-        first = 0 if j0 == 1 else j0
-        for n in ("u", "v", "p"):
-            rows_total = ref[n].shape[0]
-            last = min(j1 + 1 if j1 == cp.ny else j1, rows_total - 1)
-            a, b = r[n], ref[n][first:last + 1]
-            if case == "cavity":
-                assert np.array_equal(a.view(np.int64), b.view(np.int64)), (n, r["rows"])
-            else:
-                np.testing.assert_allclose(a, b, rtol=0, atol=1e-9 * max(np.abs(b).max(), 1.0))
-    md, ke = s.statistics()
-    for r in res:
-        if case == "cavity":
-            assert r["stats"][0] == md
-        else:  # source mean summed per rank then all-reduced: re-associated
-            assert r["stats"][0] == pytest.approx(md, rel=1e-9)
-        assert r["stats"][1] == pytest.approx(ke, rel=1e-12)
+        assert_rank_equals(r, oref, cp)
+    assert_single_equals(s, its, oracle_run(cp, steps))
 
 
 def test_rank_path_check_every_8():
@@ -124,22 +161,15 @@ def test_overlapped_halo_exchange_equals_single_domain(case, world, ny, steps):
     cp = C.make_params(case, ny=ny, nx=96)
     res = run_ranks(cp, world, steps)
     s, its = single(cp, steps)
-    ref = {n: s.field(n) for n in ("u", "v", "p")}
+    if case == "cavity":
+        ref = {n: s.field(n) for n in FIELDS}
+        ref["its"] = its
+    else:  # the channel: each layout against the oracle with its own restated source mean
+        ref = oracle_run(cp, steps, world, ranks=True)
+        assert_single_equals(s, its, oracle_run(cp, steps))
     for r in res:
         assert r["overlapped"] > 0, "overlap path not taken"
-        if case == "cavity":
-            assert r["its"] == its
-        else:
-            assert [i for i, _ in r["its"]] == [i for i, _ in its]
-        j0, j1 = r["rows"]
-        first = 0 if j0 == 1 else j0
-        for n in ("u", "v", "p"):
-            last = min(j1 + 1 if j1 == cp.ny else j1, ref[n].shape[0] - 1)
-            a, b = r[n], ref[n][first:last + 1]
-            if case == "cavity":
-                assert np.array_equal(a.view(np.int64), b.view(np.int64)), (n, r["rows"])
-            else:
-                np.testing.assert_allclose(a, b, rtol=0, atol=1e-9 * max(np.abs(b).max(), 1.0))
+        assert_rank_equals(r, ref, cp, stats=case != "cavity")
 
 
 @pytest.mark.parametrize("delta", [-2, -1, 0, 1, 2, 3])
@@ -195,20 +225,17 @@ def test_proof_mode_on_ranks(world, nx, ny, steps, cap):
 def test_open_proof_mode_on_ranks(case, world, nx, ny, steps, cap):
     """The open cases' proof-mode launches (open.hip: 4 sweeps for the
     channel, 3 for the step on ranks) on overlapped ranks with the lagged,
-    all-reduced test, against one domain with exact residuals: iteration
-    counts equal; fields to 1e-9 (the source's mean removal is summed per rank
-    and all-reduced, a re-association)."""
+    all-reduced test, and one domain with exact residuals: each against the
+    red-black oracle with its own layout's source mean restated (summed per
+    rank and all-reduced in rank order; one strip's tree sum), bit for bit,
+    residuals included; iteration counts equal between the two."""
     kw = {"max_iters": cap} if cap else {}
     cp = C.make_params(case, nx=nx, ny=ny, **kw)
     s, its = single(cp, steps, small_solve="off", proof_test="off", tuning={"tile_rounds": 0, "resident": 0})
-    ref = {n: s.field(n) for n in ("u", "v", "p")}
+    assert_single_equals(s, its, oracle_run(cp, steps))
     res = run_ranks(cp, world, steps, proof_test="on")
+    ref = oracle_run(cp, steps, world, ranks=True)
     for r in res:
         assert r["overlapped"] > 0
         assert [i for i, _ in r["its"]] == [i for i, _ in its]
-        j0, j1 = r["rows"]
-        first = 0 if j0 == 1 else j0
-        for n in ("u", "v", "p"):
-            last = min(j1 + 1 if j1 == cp.ny else j1, ref[n].shape[0] - 1)
-            a, b = r[n], ref[n][first:last + 1]
-            np.testing.assert_allclose(a, b, rtol=0, atol=1e-9 * max(np.abs(b).max(), 1.0))
+        assert_rank_equals(r, ref, cp)

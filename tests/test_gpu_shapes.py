@@ -7,7 +7,8 @@ Every comparison is bit for bit: iteration counts, residuals, fields,
 statistics, log lines and frame hashes. There is no tolerance in this file.
 Two sums are re-associated by design in the red-black order only (a tree sum
 on the GPU, a sequential one in the reference): the open cases' source mean
-and the kinetic energy. They are held to 1e-12 in
+and the kinetic energy. They are held to their restated order
+(tests/rb_sums.py), bit for bit, in
 test_gpu_parity.py::test_stencil_phases_at_launch_edges and left out here: a
 red-black step of an open case runs by phases with the oracle solving the
 GPU's own source (everything else of the step - predictor, boundary rules,

@@ -2,13 +2,12 @@
 whole timesteps bit-exact against the oracle's red-black restatement and
 against the multi-launch kernels (small_solve="off") on the reference's own grids
 (cavity 63², channel 93x31, step 256x32) and BASELINE configs[0] (128²) —
-the open cases against the oracle to 1e-8 (their source mean is re-associated)
-and bit-exact against the multi-launch path — the
+the open cases with the source mean's tree sum restated for the oracle
+(tests/rb_sums.py), so bit-exact as well — the
 stop rule with check_every > 1, and the size limit (a grid just over it takes
 the multi-launch path with the same results)."""
 from __future__ import annotations
 
-import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -16,6 +15,7 @@ pytestmark = pytest.mark.gpu
 import cfd_amd as C  # noqa: E402
 import check_every_cases as F  # noqa: E402
 import oracle as O  # noqa: E402
+import rb_sums as R  # noqa: E402
 from test_gpu_parity import assert_bits, ofield  # noqa: E402
 
 
@@ -24,7 +24,7 @@ def run_gpu(cp, steps, small=True, cavity=True, **kw):
     if cavity:  # cavity-01.cpp:380 (the open cases apply their BCs in the constructor)
         g.applyBoundaryConditions()
     its = [g.step() for _ in range(steps)]
-    fields = {n: g.field(n).copy() for n in ("u", "v", "p")}
+    fields = {n: g.field(n).copy() for n in ("u", "v", "p", "src")}
     tm = g.timing()
     g.close()
     return its, fields, tm
@@ -45,20 +45,16 @@ def test_small_solve_bitexact_vs_oracle_and_multi_launch(case, kw, steps):
     o = O.Oracle(cp, ordering=O.RB)
     if case != "cavity":
         o.velocity_bc(False)
-    its_o = [o.step() for _ in range(steps)]
-    if cav:  # bit-exact
-        assert its_s == its_o
-        for n in ("u", "v", "p"):
-            assert_bits(f_s[n], ofield(o, n, cp), f"{case} small vs oracle {n}")
-    else:  # the source's mean is a tree sum on the GPU, a sequential one in the oracle
-        assert [i for i, _ in its_s] == [i for i, _ in its_o]
-        for n in ("u", "v", "p"):
-            ref = ofield(o, n, cp)
-            np.testing.assert_allclose(f_s[n], ref, rtol=0, atol=1e-8 * np.abs(ref).max(), err_msg=n)
+    # (the open cases' source mean: the GPU's tree sum, restated for one strip)
+    hook = None if cav else R.source_hook(o, R.strips_of(cp.ny, 1))
+    its_o = [o.step(source_total=hook) for _ in range(steps)]
+    assert its_s == its_o
+    for n in ("u", "v", "p", "src"):
+        assert_bits(f_s[n], ofield(o, n, cp), f"{case} small vs oracle {n}")
     its_m, f_m, tm_m = run_gpu(cp, steps, small=False, cavity=cav)
     assert tm_m.poisson_launches > steps
     assert its_m == its_s
-    for n in ("u", "v", "p"):
+    for n in ("u", "v", "p", "src"):
         assert_bits(f_s[n], f_m[n], f"{case} small vs multi-launch {n}")
 
 
